@@ -13,11 +13,15 @@ Scaling: weak by default (every rank processes its own `--pairs` read pairs, dif
 `--pairs` over the ranks (BASELINE config #4).  With N > 1 the other mode is measured in the same run and reported as
 `other_scaling`.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+A plain run (no --full) sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the line; the
+index and transcriptome of the workload come from the cache that `build()` fills (`--prepare-only`).  Rank 0 prints ONE JSON line.
+Besides the contract fields it carries
   roofline           -- the dominant kernel by time, kernel A (k_match_v3): SURVEY.md 8(d)'s algorithmic bytes of the launch / its
                         HIP-event duration vs the 8 TB/s HBM peak; roofline_em: one EM round (LDS-resident: against the LDS pipe,
                         with the HBM-equivalent figure next to it); roofline_finalize: the EC resolution kernels
-  cpu_baseline       -- the unmodified reference (oracle/_ref, built from /root/reference) on this box's host cores: the stage clocks of the
+Everything below runs only with --full (their opt-in flags such as --bootstraps B or --multi-parity also work without it):
+  random_line_ceiling -- (in roofline) a run of kamd_debug_random_lines of its own: the rate of dependent random 64-byte reads
+  cpu_baseline       -- the unmodified reference (oracle/_ref, built by oracle/Makefile) on this box's host cores: the stage clocks of the
                         full-size parity leg's own run (all pairs of the configuration, pseudoalignment and EM seconds); a run on a bounded sample of
                         the same reads when that leg is off
   parity_check       -- the GPU path against the unmodified reference run deterministically (-t 1, oracle/_ref/dump_ec) on a
@@ -36,8 +40,8 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                         pairs; a 3' quality tail) on 8 M pairs with ALL of them through the reference: its figures, parity verdict and CPU baseline
   gencode_size       -- a child run on a GENCODE-sized index (46 000 genes: ~444 k transcripts), prefix and tail parity
 `--workload yeast` is BASELINE config #2 (10 M single-end reads, ~6 k transcripts); `--workload stress` the stress workload on its own.
-N > 1 (no flags needed): `multi_rank_parity` (the merged result of the ranks on 200 k pairs per rank against the reference), a `cpu_baseline`,
-`breakdown_ms.collective_ms`.
+N > 1: `breakdown_ms.collective_ms`; with --full also `other_scaling`, `multi_rank_parity` (the merged result of the ranks on 200 k pairs
+per rank against the reference) and a `cpu_baseline`.
 """
 from __future__ import annotations
 
@@ -53,7 +57,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-CACHE = os.environ.get("KAMD_BENCH_CACHE", "/tmp/kallisto_amd_cache")
+CACHE = os.environ.get("KAMD_BENCH_CACHE", "/tmp/kallisto_amd_cache")   # scratch: FASTQ files, reference outputs
+# the prepared workloads (transcriptome + index: minutes of CPU to build) outlive the run: build() fills this with --prepare-only
+WORKLOAD_CACHE = os.environ.get("KAMD_BENCH_CACHE") or os.path.join(
+    os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache"), "kallisto_amd", "bench")
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
 REF_BIN = os.path.join(ROOT, "oracle", "_ref", "kallisto")
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 
@@ -90,11 +98,19 @@ def wait_for(path, timeout=3600):
 
 
 def prepare_workload(name: str, genes: int, is_builder: bool):
-    """Synthetic transcriptome + index built by the reference binary; cached under CACHE."""
+    """Synthetic transcriptome + index built by the reference binary; cached under WORKLOAD_CACHE."""
     from kallisto_amd import synth
-    os.makedirs(CACHE, exist_ok=True)
+    cache = WORKLOAD_CACHE
+    try:
+        os.makedirs(cache, exist_ok=True)
+        if not os.access(cache, os.W_OK):
+            raise OSError(f"{cache} is not writable")
+    except OSError as e:   # (a home directory that cannot be written: the scratch directory, as before)
+        log(f"workload cache: {e}; using {CACHE}")
+        cache = CACHE
+        os.makedirs(cache, exist_ok=True)
     tag = f"{name}_g{genes}_v1"
-    npz, idx, done = (os.path.join(CACHE, tag + ext) for ext in (".npz", ".idx", ".done"))
+    npz, idx, done = (os.path.join(cache, tag + ext) for ext in (".npz", ".idx", ".done"))
     if not os.path.exists(done):
         if is_builder:
             t0 = time.time()
@@ -109,7 +125,7 @@ def prepare_workload(name: str, genes: int, is_builder: bool):
             log(f"synthetic transcriptome: {len(seqs)} transcripts, {cat.size/1e6:.1f} Mbp in {time.time()-t0:.0f}s")
             if not os.path.exists(REF_BIN):
                 raise RuntimeError(f"{REF_BIN} missing: the index is built by the reference binary (make -C oracle ref)")
-            fa = os.path.join(CACHE, tag + ".fa")
+            fa = os.path.join(cache, tag + ".fa")
             synth.write_fasta(fa, seqs)
             t0 = time.time()
             threads = min(effective_cpus(), 32)
@@ -644,6 +660,25 @@ def compact_table_leg(idx_path, compact_dir, n, L, paired, steps, warmup, device
         shutil.rmtree(compact_dir, ignore_errors=True)
 
 
+def dump_outputs(res, directory):
+    """--dump-outputs: what a caller of the timed path receives from its last step (kallisto_amd.quant's QuantResult without the ECs, which
+    the timed steps leave on the device), one float64 .npy per field.  An array that would take the files past DUMP_MAX_BYTES is replaced
+    by a fixed sample of its entries (seeded; the indices go beside it as <name>_index.npy)."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"est_counts": res.est_counts, "tpm": res.tpm, "eff_lens": res.eff_lens, "alpha_before_zeroes": res.alpha_before_zeroes,
+              "flens": res.flens, "n_processed": [res.n_processed], "em_rounds": [res.em_rounds]}
+    arrays = {k: np.asarray(v, np.float64).ravel() for k, v in arrays.items()}
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES
+    share = DUMP_MAX_BYTES // (2 * len(arrays)) // 8   # entries per array when sampled: value + index, both float64
+    for name, a in arrays.items():
+        if over and a.size > share:
+            keep = np.sort(np.random.default_rng(12345).choice(a.size, share, replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), keep.astype(np.float64))
+            a = a[keep]
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log(f"outputs of the last step written to {directory}: {', '.join(arrays)}")
+
+
 def bench_line_digest(d):
     """the figures of a bench line (value, step time, break-down, roofline fraction, CPU baseline, parity verdicts) without its prose"""
     keep = {k: d.get(k) for k in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "dtype", "breakdown_ms", "counters")}
@@ -795,7 +830,7 @@ def config2_leg(timeout_s=900):
     """BASELINE config #2 (yeast-like transcriptome, 10 M single-end reads, --single -l 200 -s 20) as a child run of this script: its line, cut
     down to the figures, for the line of config #3.  Never raises."""
     try:
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", "yeast", "--steps", "5", "--warmup", "2", "--end-to-end", "0", "--no-pinned-pipeline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "yeast", "--steps", "5", "--warmup", "2", "--end-to-end", "0", "--no-pinned-pipeline",
                "--no-compact-leg", "--no-config2", "--bootstraps", "0"]
         keep = bench_line_digest(run_child(cmd, timeout_s))
         keep["command"] = "python bench.py " + " ".join(cmd[2:])
@@ -808,7 +843,7 @@ def stress_leg(timeout_s=900, pairs=8_000_000):
     """The stress workload (synth.human_stress + off-transcriptome reads + quality tails) as a child run of this script with ALL its pairs through
     the unmodified reference (FullSizeParity): its line, cut down to the figures, for the line of config #3.  Never raises."""
     try:
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", "stress", "--pairs", str(pairs), "--steps", "6", "--warmup", "2", "--end-to-end", "0",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "stress", "--pairs", str(pairs), "--steps", "6", "--warmup", "2", "--end-to-end", "0",
                "--no-pinned-pipeline", "--no-compact-leg", "--no-config2", "--no-stress-leg", "--bootstraps", "0", "--full-parity", "on"]
         d = run_child(cmd, timeout_s)
         keep = bench_line_digest(d)
@@ -828,7 +863,7 @@ def gencode_leg(prep, timeout_s=600):
     try:
         if prep is not None:
             prep.wait(timeout=timeout_s)
-        cmd = [sys.executable, os.path.abspath(__file__), "--genes", str(GENCODE_GENES), "--steps", "6", "--warmup", "2", "--end-to-end", "0", "--no-pinned-pipeline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--genes", str(GENCODE_GENES), "--steps", "6", "--warmup", "2", "--end-to-end", "0", "--no-pinned-pipeline",
                "--no-compact-leg", "--no-config2", "--no-stress-leg", "--no-gencode-leg", "--bootstraps", "0", "--full-parity", "off", "--no-cpu-baseline"]
         d = run_child(cmd, timeout_s)
         keep = bench_line_digest(d)
@@ -919,21 +954,26 @@ def main():
                          "workload with the structure of a real transcriptome (synth.human_stress: repeat families in the UTRs, paralog families, poly-A "
                          "tails -> one connected component with half of the EC matrix) and the reads the other workloads lack: 12 %% off-transcriptome "
                          "pairs, a 3' quality tail of errors")
-    ap.add_argument("--prepare-only", action="store_true", help="build and cache the workload's transcriptome and index, then exit (the default run prepares the "
-                    "GENCODE-sized index in the background this way)")
+    ap.add_argument("--prepare-only", action="store_true", help="build and cache the workload's transcriptome and index, then exit (build() runs it for "
+                    "the workloads the benchmark uses, so that a run starts from the cache)")
     ap.add_argument("--no-gencode-leg", action="store_true", help="skip the child run on a GENCODE-sized index (46 000 genes, ~444 k transcripts) that the default one-GPU run of config #3 appends")
     ap.add_argument("--no-stress-leg", action="store_true", help="skip the child run of the stress workload that the default one-GPU run of config #3 appends")
     ap.add_argument("--genes", type=int, default=None, help="scale of the synthetic transcriptome (default: full config)")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N > 1: weak = --pairs per GPU (default); strong = --pairs in total, sharded over the GPUs (BASELINE config #4). "
                          "The other mode is measured too and reported in the same line.")
-    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="pairs (reads) given to the CPU reference (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run everything beside the headline: CPU reference baseline, parity legs against the "
+                    "reference (prefix, tail, full size), bootstraps, the random-line ceiling of the roofline, the stress and GENCODE-size child runs; "
+                    "N > 1: the other scaling mode and the multi-rank parity sample.  Without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last step computed (est_counts, tpm, "
+                    "eff_lens, alpha_before_zeroes, flens, n_processed, em_rounds) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-sample", type=int, default=8_000_000, help="pairs (reads) given to the CPU reference (0 = skip; --full only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--parity-sample", type=int, default=200_000,
-                    help="pairs of the CPU sample that also go through the reference at -t 1 for the parity gate")
+    ap.add_argument("--parity-sample", type=int, default=None,
+                    help="pairs of the CPU sample that also go through the reference at -t 1 for the parity gate (default: 200 000 with --full, else 0)")
     ap.add_argument("--bootstraps", type=int, default=None,
                     help="BASELINE config #5: also time B bootstrap replicates (multinomial resample + EM), split over the ranks "
-                         "(default: 100 on one GPU -- about a second --, 0 on several)")
+                         "(default: 100 on one GPU with --full -- about a second --, else 0)")
     ap.add_argument("--in-flight", type=int, default=1, help="2: also measure two samples in flight on one GPU (two contexts / streams); reported "
                     "beside the headline value, never as it")
     ap.add_argument("--end-to-end", type=int, default=None, help="run the C++ front-end from FASTQ files with this many pairs / reads (N = 1 only; 0 = skip; default: 0, "
@@ -952,13 +992,19 @@ def main():
     ap.add_argument("--full-parity", default="auto", choices=["auto", "on", "off"],
                     help="N = 1: the WHOLE input also goes through the unmodified reference (written as FASTQ while it is generated; oracle/_ref/dump_ec on all "
                          "cores in the background): EC multiset of the whole run, EM round count and abundances at full size; the same files feed the full-size "
-                         "end-to-end legs.  auto = on for the full BASELINE configuration, off for reduced ones")
+                         "end-to-end legs.  auto = on for the full BASELINE configuration with --full, off otherwise")
     ap.add_argument("--extras", action="store_true", help="N = 1: also run the side measurements that are not part of the line (they go to the detail file): the pinned pipeline, "
                     "the other k-mer table layouts (tools/compact_table_leg.py), BASELINE config #2 as a child run, the C++ front-end from FASTQ files (--end-to-end, 8 M pairs)")
     ap.add_argument("--detail-file", default=None, help="where the detail document goes (default: bench_detail.json beside this script, or $KAMD_BENCH_DETAIL)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if not args.extras:
         args.no_compact_leg = args.no_config2 = args.no_pinned_pipeline = True
+    if not args.full:
+        args.no_cpu_baseline = args.no_stress_leg = args.no_gencode_leg = True
+    if args.parity_sample is None:
+        args.parity_sample = 200_000 if args.full else 0
     if args.end_to_end is None:
         args.end_to_end = 8_000_000 if args.extras else 0
     if args.gpus > 1 and "RANK" not in os.environ and "LOCAL_RANK" not in os.environ:
@@ -1003,7 +1049,7 @@ def main():
             dist.init_process_group(backend)
 
     if args.bootstraps is None:
-        args.bootstraps = 100 if world == 1 else 0
+        args.bootstraps = 100 if world == 1 and args.full else 0
     paired = args.workload != "yeast"
     stress = args.workload == "stress"
     genes = args.genes or (20000 if paired else 6000)
@@ -1039,7 +1085,7 @@ def main():
     tail_sample = None # last pairs: parity of the tail
     spool = None
     full_size = genes == (20000 if paired else 6000) and n_arg == n_default
-    if rank == 0 and world == 1 and (args.full_parity == "on" or (args.full_parity == "auto" and full_size)) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "dump_ec")):
+    if rank == 0 and world == 1 and (args.full_parity == "on" or (args.full_parity == "auto" and full_size and args.full)) and os.path.exists(os.path.join(ROOT, "oracle", "_ref", "dump_ec")):
         need = n_gen * per * (2 * L + 70) + (8 << 30)
         os.makedirs(CACHE, exist_ok=True)
         if shutil.disk_usage(CACHE).free > need:
@@ -1131,6 +1177,8 @@ def main():
         return el, res, profs
 
     elapsed, res, profs = timed(n)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
     pr = profs[-1]
     align_ms = [p["align_kernel_ms"] for p in profs]; em_ms = [p["em_ms"] for p in profs]
     cls_ms = [p["classify_ms"] for p in profs]; fin_ms = [p["finalize_ms"] for p in profs]
@@ -1139,7 +1187,7 @@ def main():
     st = res.stats
     total_items = n * world * args.steps
     other = None
-    if world > 1:   # the other scaling mode, same run
+    if world > 1 and args.full:   # the other scaling mode, same run
         n_o = n_strong if args.scaling == "weak" else n_weak
         el_o, _, _ = timed(n_o)
         other = {"scaling": "strong" if args.scaling == "weak" else "weak", "pairs_per_gpu": n_o, "pairs_total_per_step": n_o * world,
@@ -1378,14 +1426,15 @@ def main():
         # the rate does not depend on the footprint or the access size -- profiles/README.md); the kernel's requests are its
         # bucket lines + text reads + the packed reads
         ceiling = None
-        try:
-            g_s, _ = ctx.random_lines(256 * 6, 256, 256)
-            req_bytes = 64.0 * (st["n_bucket_reads"] + st["n_text_hits"])
-            line_gbs = (req_bytes + n * per * rec * 4.0) / (a_ms * 1e-3) / 1e9
-            ceiling = {"GB/s_in_64B_lines": round(g_s, 1), "kernel_GB/s_in_64B_lines": round(line_gbs, 1), "frac": round(line_gbs / g_s, 4),
-                       "note": "kamd_debug_random_lines at 24 wavefronts/CU; a request-rate ceiling (same for 64 MB .. 2.4 GB footprints, 8 .. 64 B accesses)"}
-        except Exception as e:   # diagnostic only
-            ceiling = {"error": str(e)}
+        if args.full:   # (a measurement of its own on the GPU)
+            try:
+                g_s, _ = ctx.random_lines(256 * 6, 256, 256)
+                req_bytes = 64.0 * (st["n_bucket_reads"] + st["n_text_hits"])
+                line_gbs = (req_bytes + n * per * rec * 4.0) / (a_ms * 1e-3) / 1e9
+                ceiling = {"GB/s_in_64B_lines": round(g_s, 1), "kernel_GB/s_in_64B_lines": round(line_gbs, 1), "frac": round(line_gbs / g_s, 4),
+                           "note": "kamd_debug_random_lines at 24 wavefronts/CU; a request-rate ceiling (same for 64 MB .. 2.4 GB footprints, 8 .. 64 B accesses)"}
+            except Exception as e:   # diagnostic only
+                ceiling = {"error": str(e)}
         out = {
             "metric": ("M paired-end reads/sec quantified (human txome index, stress workload)" if stress else "M paired-end reads/sec quantified (human txome index)") if paired
                       else "M single-end reads/sec quantified (yeast-sized index)",

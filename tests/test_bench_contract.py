@@ -131,3 +131,44 @@ def test_self_launcher_passes_only_the_short_line_through(tmp_path):
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1 and json.loads(lines[0])["n_gpus"] == 2 and json.loads(lines[0])["cpu_baseline"]["value"] == 0.2
+
+
+def test_dump_outputs_writes_float64_files_within_the_bound(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 .npy per field of the last step's result; past the byte bound an array becomes a fixed, seeded sample of its
+    entries with the indices beside it, the same sample on every run"""
+    import types
+    import numpy as np
+    T = 5000
+    res = types.SimpleNamespace(est_counts=np.linspace(0.0, 9.0, T), tpm=np.full(T, 200.0), eff_lens=np.arange(T, dtype=np.float64) + 0.5,
+                                alpha_before_zeroes=np.linspace(0.0, 9.0, T), flens=np.arange(1000, dtype=np.uint32), n_processed=123, em_rounds=52)
+    bench.dump_outputs(res, str(tmp_path / "a"))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert set(got) == {"est_counts", "tpm", "eff_lens", "alpha_before_zeroes", "flens", "n_processed", "em_rounds"}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["est_counts"], res.est_counts) and np.array_equal(got["flens"], np.arange(1000)) and got["n_processed"].tolist() == [123]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 64 << 10)
+    for d in ("b", "c"):
+        bench.dump_outputs(res, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in files) <= 64 << 10   # (128 = the .npy header)
+    assert files == sorted(os.listdir(tmp_path / "c")) and "est_counts_index.npy" in files and "em_rounds_index.npy" not in files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+    idx = np.load(tmp_path / "b" / "eff_lens_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "b" / "eff_lens.npy"), res.eff_lens[idx]) and np.all(np.diff(idx) > 0)
+
+
+def test_bench_options_of_a_plain_and_a_full_run():
+    """--full and --dump-outputs are there; --steps below one is refused before anything is set up"""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 0 and b"--full" in p.stdout and b"--dump-outputs" in p.stdout
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert p.returncode == 2 and b"--steps" in p.stderr and not p.stdout.strip()
+
+
+def test_child_legs_are_full_runs(monkeypatch):
+    """the stress, GENCODE-size and config #2 child runs carry --full: their parity legs and CPU baselines are what they report"""
+    seen = []
+    monkeypatch.setattr(bench, "run_child", lambda cmd, t: seen.append(cmd) or {"value": 1.0})
+    bench.stress_leg(); bench.gencode_leg(None); bench.config2_leg()
+    assert len(seen) == 3 and all("--full" in cmd for cmd in seen)

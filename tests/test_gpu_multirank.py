@@ -192,7 +192,7 @@ def test_bench_two_ranks_on_one_gpu_with_parity(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "KAMD_BENCH_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--genes", "1500", "--pairs", "400000", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--multi-parity", "--detail-file", str(tmp_path / "detail.json")], cwd=ROOT, env=env, stdout=subprocess.PIPE,
+                        "--full", "--no-cpu-baseline", "--multi-parity", "--detail-file", str(tmp_path / "detail.json")], cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -215,7 +215,7 @@ def test_bench_two_ranks_on_one_gpu_with_parity(tmp_path):
 
 
 def test_bench_two_ranks_without_flags_carries_parity_and_cpu_baseline(tmp_path):
-    """`KAMD_BENCH_SHARE_GPU=1 python bench.py --gpus 2` with no parity / baseline flag at all -- what the driver's scaling run passes -- must print a
+    """`KAMD_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --full` with no parity / baseline flag beyond that must print a
     line with `roofline`, a `cpu_baseline` and a parity verdict: the merged result of the ranks on a bounded sample (here 100 k pairs per rank) against the
     unmodified reference on those pairs in rank order."""
     import json
@@ -228,7 +228,7 @@ def test_bench_two_ranks_without_flags_carries_parity_and_cpu_baseline(tmp_path)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "KAMD_BENCH_BACKEND"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--genes", "1500", "--pairs", "300000", "--steps", "2", "--warmup", "1",
-                        "--parity-sample", "100000", "--detail-file", str(tmp_path / "detail.json")], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        "--full", "--parity-sample", "100000", "--detail-file", str(tmp_path / "detail.json")], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                        timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     text = [ln for ln in p.stdout.decode().splitlines() if ln.strip()][-1]

@@ -117,6 +117,14 @@ int kamd_index_load(const char* path, int threads, kamd_index** out);
 #define KAMD_TABLE_COMPACT 1
 #define KAMD_TABLE_AUTO 2
 int kamd_index_load_layout(const char* path, int threads, int layout, double load, kamd_index** out);
+/* The same without the k-mer table: the index is parsed as kamd_index_load_layout parses it (unitigs, D-list keys, node records, transcript
+ * sets, blocks, targets, on-list, unitig text), but the table, its two aux arrays, the D-list table and the dummy hit are left to
+ * kamd_index_upload, which builds them on the device for the layout and load factor given here (layout -1 = what kamd_index_load reads from
+ * the environment).  The device-built table is, byte for byte, the one kamd_index_load_layout builds with threads = 1 (the keys of a home bucket
+ * in ascending text position); with more threads the host's order inside a home bucket depends on scheduling, the device's never does.
+ * kamd_index_get_view on such an index reports table == slot_block == slot_dist == dtable == NULL and n_buckets == 0 (kamd_ctx_table_info says
+ * what was built); kamd_index_save refuses it (-1).  A flattened file holds its tables already and is loaded as kamd_index_load_layout loads it. */
+int kamd_index_load_deferred(const char* path, int threads, int layout, double load, kamd_index** out);
 /* The flattened tables as a file: building them from a kallisto index takes seconds; kamd_index_save writes them once and
  * kamd_index_load recognises such a file by its magic and reads it back with plain reads (same kamd_index).  Native byte order,
  * format-versioned; not a replacement for the kallisto index, which stays the source of truth. */
@@ -185,6 +193,24 @@ int kamd_ctx_create(int device, void* hip_stream, kamd_ctx** out);
 void kamd_ctx_destroy(kamd_ctx*);
 int kamd_index_upload(kamd_ctx*, const kamd_index*);
 int kamd_ec_reset(kamd_ctx*);  /* forget all EC counts (a new MinCollector, src/MinCollector.h:22) */
+/* The k-mer table of the context's device index, after either kind of upload: its geometry (what kamd_index_view reports for an index loaded
+ * with its table), whether kamd_index_upload built it on the device, and then what the build took (HIP events on the context stream: in all,
+ * and per stage -- count + scan rounds, placement, ordering of the home groups, reconstruction of the slots, D-list table + dummy hit). */
+typedef struct {
+  uint64_t n_buckets, pad_buckets;
+  uint32_t table_layout, slots_per_bucket, tag_q, tag_dsh, tag_w;
+  uint64_t n_dbuckets, dpad_buckets;
+  uint64_t dummy_slot;
+  uint32_t dummy_uec, dummy_strand;
+  int32_t built_on_device;      /* 1 = by kamd_index_upload from a deferred index, 0 = uploaded from the host */
+  int32_t build_rounds;         /* count + scan rounds (1 unless the compact table had to grow or fell back to the wide one) */
+  float build_ms;               /* 0 when the tables were uploaded */
+  float build_count_ms, build_place_ms, build_order_ms, build_fill_ms, build_dlist_ms;
+} kamd_table_info;
+int kamd_ctx_table_info(kamd_ctx*, kamd_table_info* out);
+/* the device tables into host arrays of (n_buckets + pad_buckets) * 8 u64, (n_buckets + pad_buckets) * slots_per_bucket u32 (twice) and
+ * (n_dbuckets + dpad_buckets) * 8 u64; any pointer may be null */
+int kamd_ctx_table_download(kamd_ctx*, uint64_t* table, uint32_t* slot_block, uint32_t* slot_dist, uint64_t* dtable);
 
 /* ---- reads: 2-bit packing of one parsed batch (what fetchSequences hands to processBuffer) ----
  * Record layout per read: words_per_read u32 of 2-bit bases (base i at bits 2*(i&15) of word i>>4; A0 C1 G2 T3,

@@ -76,6 +76,15 @@ class _Profile(C.Structure):
                 ("last_merge_ms", C.c_float), ("em_collective_ms", C.c_float), ("em_collectives", C.c_uint32), ("n_overflow_second_pass", C.c_uint64), ("last_em_giant_pieces", C.c_uint64)]
 
 
+class _TableInfo(C.Structure):
+    """kamd_table_info: geometry of the context's device k-mer table, and what its build took when kamd_index_upload built it."""
+    _fields_ = [("n_buckets", C.c_uint64), ("pad_buckets", C.c_uint64), ("table_layout", C.c_uint32), ("slots_per_bucket", C.c_uint32),
+                ("tag_q", C.c_uint32), ("tag_dsh", C.c_uint32), ("tag_w", C.c_uint32), ("n_dbuckets", C.c_uint64), ("dpad_buckets", C.c_uint64),
+                ("dummy_slot", C.c_uint64), ("dummy_uec", C.c_uint32), ("dummy_strand", C.c_uint32), ("built_on_device", C.c_int32),
+                ("build_rounds", C.c_int32), ("build_ms", C.c_float), ("build_count_ms", C.c_float), ("build_place_ms", C.c_float),
+                ("build_order_ms", C.c_float), ("build_fill_ms", C.c_float), ("build_dlist_ms", C.c_float)]
+
+
 class _FastqUnit(C.Structure):
     _fields_ = [("d_words", C.c_void_p), ("d_len", C.c_void_p), ("n_items", C.c_uint64), ("max_len", C.c_int32), ("status", C.c_int32),
                 ("first_bad_record", C.c_uint64)]
@@ -103,6 +112,7 @@ _SYMBOLS = {
     "kamd_abi_version": (C.c_uint32, []),
     "kamd_index_load": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]),
     "kamd_index_load_layout": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
+    "kamd_index_load_deferred": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
     "kamd_index_free": (None, [C.c_void_p]),
     "kamd_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kamd_index_get_view": (C.c_int, [C.c_void_p, C.POINTER(_View)]),
@@ -113,6 +123,8 @@ _SYMBOLS = {
     "kamd_ctx_get_tuning": (C.c_int, [C.c_void_p, C.POINTER(Tuning)]),
     "kamd_index_upload": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kamd_ec_reset": (C.c_int, [C.c_void_p]),
+    "kamd_ctx_table_info": (C.c_int, [C.c_void_p, C.POINTER(_TableInfo)]),
+    "kamd_ctx_table_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kamd_ec_track_order": (C.c_int, [C.c_void_p, C.c_int]),
     "kamd_packed_record_words": (C.c_uint64, [C.c_int32]),
     "kamd_pack_reads_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
@@ -237,12 +249,18 @@ class Index:
 
     TABLE_LAYOUTS = {"wide": 0, "compact": 1, "auto": 2}
 
-    def __init__(self, path: str, threads: int = 0, table_layout: str | None = None, table_load: float = 0.0):
+    def __init__(self, path: str, threads: int = 0, table_layout: str | None = None, table_load: float = 0.0, deferred: bool = False):
         """table_layout: None = kamd_index_load (the environment's KAMD_TABLE_LAYOUT, default auto: compact when it fits); "wide" / "compact" / "auto" =
-        kamd_index_load_layout with that layout of the k-mer table (and table_load as the compact table's load factor, 0 = the library's choice)."""
+        kamd_index_load_layout with that layout of the k-mer table (and table_load as the compact table's load factor, 0 = the library's choice).
+        deferred: kamd_index_load_deferred -- the k-mer table is not built here but by Context.upload on the device (Context.table_info says what
+        was built); the view's table pointers are null."""
         lib = load_library()
         self._h = C.c_void_p()
-        if table_layout is None:
+        self.deferred = bool(deferred)
+        if deferred:
+            _check(lib.kamd_index_load_deferred(os.fsencode(path), threads, -1 if table_layout is None else self.TABLE_LAYOUTS[table_layout], float(table_load),
+                                                C.byref(self._h)), "kamd_index_load_deferred")
+        elif table_layout is None:
             _check(lib.kamd_index_load(os.fsencode(path), threads, C.byref(self._h)), "kamd_index_load")
         else:
             _check(lib.kamd_index_load_layout(os.fsencode(path), threads, self.TABLE_LAYOUTS[table_layout], float(table_load), C.byref(self._h)),
@@ -317,6 +335,22 @@ class Context:
 
     def reset(self):
         _check(load_library().kamd_ec_reset(self._h), "kamd_ec_reset")
+
+    def table_info(self) -> dict:
+        """kamd_ctx_table_info: geometry of the device k-mer table; built_on_device and the build's milliseconds after the upload of a deferred index."""
+        t = _TableInfo()
+        _check(load_library().kamd_ctx_table_info(self._h, C.byref(t)), "kamd_ctx_table_info")
+        return {n: getattr(t, n) for n, _ in _TableInfo._fields_}
+
+    def table_download(self) -> dict:
+        """kamd_ctx_table_download: the device tables as host arrays {table, slot_block, slot_dist, dtable} (dtable empty without a D-list)."""
+        t = self.table_info()
+        lines = t["n_buckets"] + t["pad_buckets"]
+        out = {"table": np.zeros(lines * 8, np.uint64), "slot_block": np.zeros(lines * t["slots_per_bucket"], np.uint32),
+               "slot_dist": np.zeros(lines * t["slots_per_bucket"], np.uint32), "dtable": np.zeros((t["n_dbuckets"] + t["dpad_buckets"]) * 8, np.uint64)}
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+        _check(load_library().kamd_ctx_table_download(self._h, p(out["table"]), p(out["slot_block"]), p(out["slot_dist"]), p(out["dtable"])), "kamd_ctx_table_download")
+        return out
 
     def tune(self, **kw):
         """kamd_ctx_tune: e.g. tune(text_verify=False), tune(em_form="streamed", em_entries_per_lane=16).  Returns the tuning in force."""

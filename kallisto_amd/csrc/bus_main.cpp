@@ -49,6 +49,7 @@ void usage_bus() {
             << "    --fr-stranded / --rf-stranded / --unstranded\n"
             << "    --union, --no-jump        As in quant\n"
             << "-t, --threads=INT             Host threads (default: 1)\n"
+            << "    --index-build=host|device As in quant: where the k-mer table is built (default: host)\n"
             << "    --bus-per-read            output.bus with one record per pseudoaligned read (count 1), as the reference writes it; by default\n"
             << "                              the records of a sample and class are collapsed into one with their number in `count` -- what\n"
             << "                              `bustools sort` makes of the reference's file.  Either way the records are sorted by barcode and\n"
@@ -71,13 +72,17 @@ int bus_main(int argc, char** argv) {
   if (argc == 2) { usage_bus(); return 0; }
   std::string index, output, technology, batch_file, val;
   std::vector<std::string> files;
-  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false;
+  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false;
   int strand = 0, threads = 1;
   uint64_t batch = 4u << 20;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     if (take(a, "-i", "--index", i, argc, argv, val)) index = val;
     else if (take(a, "-o", "--output-dir", i, argc, argv, val)) output = val;
+    else if (take(a, nullptr, "--index-build", i, argc, argv, val)) {
+      if (val != "host" && val != "device") { std::cerr << "Error: --index-build expects host or device" << std::endl; return 1; }
+      index_build_device = val == "device";
+    }
     else if (take(a, "-x", "--technology", i, argc, argv, val)) { technology = val; for (auto& ch : technology) ch = (char)toupper(ch); }
     else if (take(a, "-t", "--threads", i, argc, argv, val)) threads = atoi(val.c_str());
     else if (take(a, "-B", "--batch", i, argc, argv, val)) batch_file = val;
@@ -168,7 +173,8 @@ int bus_main(int argc, char** argv) {
   (void)hipSetDeviceFlags(hipDeviceScheduleBlockingSync);   // (see quant_main.cpp)
   threads = std::min(threads, effective_cpus());
   kamd_index* idx = nullptr;
-  KX(kamd_index_load(index.c_str(), threads, &idx));
+  if (index_build_device) KX(kamd_index_load_deferred(index.c_str(), threads, -1, 0.0, &idx));   // (the table is built by kamd_index_upload)
+  else KX(kamd_index_load(index.c_str(), threads, &idx));
   kamd_index_view v; KX(kamd_index_get_view(idx, &v));
   std::cerr << "\n[index] k-mer length: " << v.k << "\n[index] number of targets: " << v.n_targets << "\n[index] number of k-mers: " << v.n_kmers << std::endl;
   kamd_ctx* ctx = nullptr;

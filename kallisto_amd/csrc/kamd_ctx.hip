@@ -208,15 +208,21 @@ extern "C" int kamd_index_upload(kamd_ctx* c, const kamd_index* hix) {
   HIPC(hipSetDevice(c->device));
   kamd_index_view v;
   if (int rc = kamd_index_get_view(hix, &v)) return rc;
+  // an index loaded with kamd_index_load_deferred brings no k-mer table: it is built on this device once everything else is here
+  const bool build_table = v.table == nullptr;
+  HIPC(hipStreamSynchronize(c->stream));
+  c->has_index = false;
   for (void* p : c->index_allocs) (void)hipFree(p);
   c->index_allocs.clear();
   DevIndex d{};
   d.k = v.k; d.n_buckets = v.n_buckets; d.n_ecs = v.n_ecs;
   d.table_layout = (int)v.table_layout; d.tag_q = v.tag_q; d.tag_dsh = v.tag_dsh; d.tag_w = v.tag_w;
   const u64 slots = (v.n_buckets + v.pad_buckets) * v.slots_per_bucket;
-  if (int rc = upload(c, (const u64*)v.table, (size_t)(v.n_buckets + v.pad_buckets) * 8, &d.table)) return rc;
-  if (int rc = upload(c, v.slot_block, slots, &d.slot_block)) return rc;
-  if (int rc = upload(c, v.slot_dist, slots, &d.slot_dist)) return rc;
+  if (!build_table) {
+    if (int rc = upload(c, (const u64*)v.table, (size_t)(v.n_buckets + v.pad_buckets) * 8, &d.table)) return rc;
+    if (int rc = upload(c, v.slot_block, slots, &d.slot_block)) return rc;
+    if (int rc = upload(c, v.slot_dist, slots, &d.slot_dist)) return rc;
+  }
   if (int rc = upload(c, v.uec_ec, v.n_uec, &d.uec_ec)) return rc;
   if (int rc = upload(c, (const u64*)v.ec_off, v.n_ecs + 1, &d.ec_off)) return rc;
   if (int rc = upload(c, v.ec_ids, v.ec_nnz, &d.ec_ids)) return rc;
@@ -274,6 +280,14 @@ extern "C" int kamd_index_upload(kamd_ctx* c, const kamd_index* hix) {
   if (v.n_dbuckets) if (int rc = upload(c, (const u64*)v.dtable, (size_t)(v.n_dbuckets + v.dpad_buckets) * 8, &d.dtable)) return rc;
   if (int rc = upload(c, v.utext, (size_t)v.utext_words, &d.utext)) return rc;
   HIPC(hipStreamSynchronize(c->stream));  // `ne` is a stack-owned staging buffer
+  kamd_table_info ti; memset(&ti, 0, sizeof ti);
+  if (build_table) { if (int rc = index_build_device(c, hix, v, &d, &ti)) return rc; }
+  else {
+    ti.n_buckets = v.n_buckets; ti.pad_buckets = v.pad_buckets; ti.table_layout = v.table_layout; ti.slots_per_bucket = v.slots_per_bucket;
+    ti.tag_q = v.tag_q; ti.tag_dsh = v.tag_dsh; ti.tag_w = v.tag_w; ti.n_dbuckets = v.n_dbuckets; ti.dpad_buckets = v.dpad_buckets;
+    ti.dummy_slot = v.dummy_slot; ti.dummy_uec = v.dummy_uec; ti.dummy_strand = v.dummy_strand;
+  }
+  c->tinfo = ti;
   c->ix = d; c->has_index = true; c->n_ecs = v.n_ecs; c->n_targets = v.n_targets;
   if (int rc = c->dense.ensure(std::max<u64>(v.n_ecs, 1) * sizeof(u32), 0, c->stream)) return rc;
   HIPC(hipMemsetAsync(c->dense.p, 0, std::max<u64>(v.n_ecs, 1) * sizeof(u32), c->stream));

@@ -5,6 +5,7 @@
 //   kamd_em.hip      the EM in all its forms (component-local k_em_sell, hybrid, streamed, CSR), bootstrap
 //   kamd_io.hip      FASTQ text in HBM -> packed reads
 //   kamd_ctx.hip     context, index upload, tuning, diagnostics, communicators and what runs over them
+//   kamd_ixbuild.hip the k-mer table built on the device (upload of an index loaded with kamd_index_load_deferred), kamd_ctx_table_*
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -235,6 +236,7 @@ struct kamd_ctx {
   std::vector<void*> index_allocs;
   u64 n_ecs = 0, n_targets = 0;
   u32 n_set_bitmaps = 0;   // index sets that also exist as bitmaps (DevIndex::bm_words)
+  kamd_table_info tinfo{}; // geometry of the device k-mer table, and what its build took when kamd_index_upload built it (kamd_ixbuild.hip)
   DBuf dense, stream_buf, rec_off, overflow_items, overflow_scratch, state, rec_slot, retry, ttable, list;
   DBuf cand, cand_off, cand_slot, ctable, clist, sizes, block_sums, tup_bound, tup_off, tup_big;
   DBuf raw2, overflow_left, stats_b;   // the second pass over the items whose class list overflowed: its raw records, what overflows again, its counters
@@ -314,6 +316,8 @@ int push_state(kamd_ctx* c);
 void apply_quant_opts(kamd_ctx* c, const kamd_quant_opts* o);
 void apply_tuning(kamd_ctx* c);
 void comm_detach_all(kamd_ctx* c);
+// kamd_ixbuild.hip
+int index_build_device(kamd_ctx* c, const kamd_index* hix, const kamd_index_view& v, DevIndex* d, kamd_table_info* info);
 // kamd_ec.hip
 int exclusive_scan(kamd_ctx* c, const u32* sizes, u64 n, u64* out, u64* d_total);
 int tuples_clear(kamd_ctx* c);

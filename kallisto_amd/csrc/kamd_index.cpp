@@ -10,6 +10,7 @@
 #include "../../include/kallisto_amd.h"
 #include "kamd_core.h"
 #include "kamd_host.h"
+#include "kamd_ixbuild.h"
 
 #include <algorithm>
 #include <atomic>
@@ -188,6 +189,10 @@ struct kamd_index {
   // identity of the kallisto index these tables were built from (size in bytes, hash of its first and last 64 KiB): written into a
   // flattened file so that one picked up beside an index can be tied to that index (kamd_flat_index_matches); 0 / 0 = unknown
   uint64_t src_size = 0, src_hash = 0;
+  // kamd_index_load_deferred: everything but table / slot_block / slot_dist / dtable and the dummy hit, which kamd_index_upload builds on the
+  // device for the layout and load factor kept here
+  bool deferred = false;
+  int req_layout = KAMD_TABLE_AUTO; double req_load = 0.0;
 };
 
 namespace {
@@ -316,14 +321,7 @@ template <class IO> void flat_fields(IO& io, kamd_index& x) {
   io.vec(x.blk_pos_off); io.vec(x.blk_posw); io.vec(x.blk_sense); io.vec(x.uec_ec); io.vec(x.ec_off); io.vec(x.ec_ids); io.vec(x.target_lens);
   io.vec(x.onlist_bits); io.vec(x.table); io.vec(x.slot_block); io.vec(x.slot_dist); io.vec(x.utext); io.vec(x.unitig_gpos); io.vec(x.dlist_keys); io.vec(x.dtable);
 }
-uint32_t bits_of(uint64_t n) { uint32_t b = 0; while (b < 64 && (n >> b)) ++b; return b; }   // bits that hold the values 0..n
-// the shifts of the compact layout for a table of nb home buckets; false: a field does not fit (kamd_core.h)
-bool compact_shifts(int k, uint64_t nb, uint64_t n_uec, uint64_t text_bases, uint32_t* q, uint32_t* dsh, uint32_t* w) {
-  *q = kamd::compact_q_of(nb);
-  *dsh = *q + (uint32_t)std::max(0, 2 * k - 32);
-  *w = *dsh + (*dsh + 4 + bits_of(n_uec) <= 64 ? 4 : 3);   // the displacement: four bits when the class ids leave room for them
-  return *w + bits_of(n_uec) <= 64 && text_bases <= kamd::COMPACT_GPOS_MASK;
-}
+using kamd::ixb::compact_shifts;   // (the geometry of the table: kamd_ixbuild.h, shared with the device builder)
 bool layout_is_consistent(const kamd_index& x) {
   if (x.layout == kamd::LAYOUT_WIDE) return x.slots == (uint32_t)kamd::BUCKET_SLOTS;
   if (x.layout != kamd::LAYOUT_COMPACT || x.slots != (uint32_t)kamd::COMPACT_SLOTS || x.n_buckets < 16) return false;
@@ -395,6 +393,7 @@ int load_flat(const char* path, int threads, kamd_index** out) {
 
 extern "C" int kamd_index_save(const kamd_index* ix, const char* path) {
   if (!ix || !path) return kamd::fail(-1, "kamd_index_save: null argument");
+  if (ix->deferred) return kamd::fail(-1, "kamd_index_save: this index was loaded without its k-mer table (kamd_index_load_deferred); load it with kamd_index_load to flatten it");
   FILE* f = fopen(path, "wb");
   if (!f) return kamd::fail(-2, std::string("kamd_index_save: could not open ") + path);
   FlatOut o{f};
@@ -423,30 +422,49 @@ extern "C" int kamd_flat_index_matches(const char* flat_path, const char* index_
 }
 
 namespace {
-int load_index_impl(const char* path, int threads, int want_compact, double compact_load, kamd_index** out, bool layout_requested);
+int load_index_impl(const char* path, int threads, int want_compact, double compact_load, kamd_index** out, bool layout_requested, bool deferred = false);
+// the layout of the k-mer table from the environment: KAMD_TABLE_LAYOUT = wide | compact | auto (auto when unset), KAMD_TABLE_LOAD
+int layout_from_env(int* want_compact, double* compact_load, bool* requested) {
+  *want_compact = KAMD_TABLE_AUTO; *compact_load = 0.0;
+  const char* e = getenv("KAMD_TABLE_LAYOUT");
+  if (e) {
+    if (!strcmp(e, "compact")) *want_compact = KAMD_TABLE_COMPACT;
+    else if (!strcmp(e, "auto")) *want_compact = KAMD_TABLE_AUTO;
+    else if (!strcmp(e, "wide")) *want_compact = KAMD_TABLE_WIDE;
+    else if (*e) return kamd::fail(-1, std::string("KAMD_TABLE_LAYOUT: wide, compact or auto expected, not ") + e);
+  }
+  if (const char* l = getenv("KAMD_TABLE_LOAD")) *compact_load = atof(l);
+  *requested = e != nullptr && *e;
+  return 0;
+}
 }
 extern "C" int kamd_index_load(const char* path, int threads, kamd_index** out) {
   // the layout of the k-mer table from the environment: KAMD_TABLE_LAYOUT = wide (default) | compact | auto, KAMD_TABLE_LOAD
   // (default since round 4: auto.  Measured on MI355X, profiles/r04_gencode_size_table_layouts.json: at GENCODE size -- 130.6 M k-mers --
   // kernel A takes 13.9 ms on the wide table (5.6 GB) and 11.7 ms on the compact one at a load of 0.6 (3.5 GB); at config #3's 56.8 M
   // k-mers 10.43 wide, 10.29 compact at 0.5, 10.55 at 0.6)
-  int want_compact = KAMD_TABLE_AUTO;
-  if (const char* e = getenv("KAMD_TABLE_LAYOUT")) {
-    if (!strcmp(e, "compact")) want_compact = KAMD_TABLE_COMPACT;
-    else if (!strcmp(e, "auto")) want_compact = KAMD_TABLE_AUTO;
-    else if (!strcmp(e, "wide")) want_compact = KAMD_TABLE_WIDE;
-    else if (*e) return kamd::fail(-1, std::string("KAMD_TABLE_LAYOUT: wide, compact or auto expected, not ") + e);
-  }
-  double compact_load = 0.0;
-  if (const char* e = getenv("KAMD_TABLE_LOAD")) compact_load = atof(e);
-  return load_index_impl(path, threads, want_compact, compact_load, out, getenv("KAMD_TABLE_LAYOUT") != nullptr && *getenv("KAMD_TABLE_LAYOUT"));
+  int want_compact; double compact_load; bool requested = false;
+  if (int rc = layout_from_env(&want_compact, &compact_load, &requested)) return rc;
+  return load_index_impl(path, threads, want_compact, compact_load, out, requested);
 }
 extern "C" int kamd_index_load_layout(const char* path, int threads, int layout, double load, kamd_index** out) {
   if (layout != KAMD_TABLE_WIDE && layout != KAMD_TABLE_COMPACT && layout != KAMD_TABLE_AUTO) return kamd::fail(-1, "kamd_index_load_layout: layout must be KAMD_TABLE_WIDE, _COMPACT or _AUTO");
   return load_index_impl(path, threads, layout, load, out, true);
 }
+extern "C" int kamd_index_load_deferred(const char* path, int threads, int layout, double load, kamd_index** out) {
+  bool requested = true;
+  if (layout == -1) { if (int rc = layout_from_env(&layout, &load, &requested)) return rc; }
+  else if (layout != KAMD_TABLE_WIDE && layout != KAMD_TABLE_COMPACT && layout != KAMD_TABLE_AUTO) return kamd::fail(-1, "kamd_index_load_deferred: layout must be KAMD_TABLE_WIDE, _COMPACT, _AUTO or -1 (the environment's)");
+  return load_index_impl(path, threads, layout, load, out, requested, true);
+}
+extern "C" int kamd_ixbuild_info_get(const kamd_index* ix, kamd_ixbuild_info* o) {
+  if (!ix || !o) return kamd::fail(-1, "kamd_ixbuild_info_get: null argument");
+  o->deferred = ix->deferred ? 1 : 0; o->layout = ix->req_layout; o->load = ix->req_load;
+  o->blk_uec = ix->blk_uec.data(); o->dlist_keys = ix->dlist_keys.data();
+  return 0;
+}
 namespace {
-int load_index_impl(const char* path, int threads, int want_compact, double compact_load_arg, kamd_index** out, bool layout_requested) {
+int load_index_impl(const char* path, int threads, int want_compact, double compact_load_arg, kamd_index** out, bool layout_requested, bool deferred) {
   if (!out) return kamd::fail(-1, "kamd_index_load: null output pointer");
   *out = nullptr;
   if (threads <= 0) {
@@ -599,16 +617,12 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
   // kernel A 10.13 / 10.26 / 10.55 ms; profiles/README.md), 0.6 beyond (fewer bytes beat fewer lines per probe there)
   // The footprint is a property of the device (MI355X: 2.4 GB, measured with kamd_debug_random_lines_span -- 54 G lines/s up to there, 28 G/s at
   // 3.6 GB; bench.py reports the live figure as random_line_ceiling), not of the library: KAMD_TABLE_KNEE_GB overrides it for another part.
-  double knee = 2.4e9;
-  if (const char* e = getenv("KAMD_TABLE_KNEE_GB")) { const double v = atof(e); if (v > 0.05 && v < 1024.0) knee = v * 1e9; }
-  const double bytes_at_1 = (double)ix->n_kmers * (64.0 / kamd::COMPACT_SLOTS);
-  const double default_load = bytes_at_1 / 0.4 <= knee ? 0.4 : bytes_at_1 / 0.5 <= knee ? 0.5 : 0.6;
-  const double compact_load = (compact_load_arg >= 0.2 && compact_load_arg <= 0.9) ? compact_load_arg : default_load;
-  bool compact = want_compact != KAMD_TABLE_WIDE;
-  const uint64_t nb_wide = std::max<uint64_t>(16, (ix->n_kmers * 2 + kamd::BUCKET_SLOTS - 1) / kamd::BUCKET_SLOTS);  // load factor 0.5 over 3-slot buckets
-  uint64_t S = compact ? kamd::COMPACT_SLOTS : kamd::BUCKET_SLOTS;
-  uint64_t nb = compact ? std::max<uint64_t>(16, (uint64_t)((double)ix->n_kmers / compact_load / (double)S) + 1) : nb_wide;
-  if (std::max(nb, nb_wide) >= 0xF0000000ULL) return kamd::fail(-3, "index: too many k-mers for 32-bit bucket numbers");
+  // The decisions themselves are in kamd_ixbuild.h: the device builder (kamd_index_upload on a deferred index) takes the same ones.
+  kamd::ixb::Geometry geo;
+  if (!kamd::ixb::geometry_init(geo, k, ix->n_kmers, want_compact, compact_load_arg)) return kamd::fail(-3, "index: too many k-mers for 32-bit bucket numbers");
+  bool& compact = geo.compact;
+  uint64_t& S = geo.S;
+  uint64_t& nb = geo.nb;
   // [0, n) in contiguous pieces, one per thread: the big arrays are first touched (and later scanned) by all threads
   auto parallel_range = [&](uint64_t n, auto&& body) {
     std::vector<std::thread> th;
@@ -619,7 +633,8 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     }
     for (auto& t : th) t.join();
   };
-  BigVec<uint32_t> fill; fill.resize(nb + 1);
+  BigVec<uint32_t> fill;
+  if (!deferred) fill.resize(nb + 1);
   auto fill_atomic = reinterpret_cast<std::atomic<uint32_t>*>(fill.data());
   // all unitigs, handed out in runs of 256; every thread has a state of its own (make()), flushed when it runs out of work (drain())
   auto run_parallel = [&](auto&& make, auto&& body, auto&& drain) {
@@ -659,7 +674,8 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
                  },
                  [&](CountState& st) { for (int i = 0; i < st.n; i++) fill_atomic[st.hb[(st.head + i) % RING]].fetch_add(1, std::memory_order_relaxed); });
   };
-  std::thread count_bg(count_pass);
+  std::thread count_bg;
+  if (!deferred) count_bg = std::thread(count_pass);   // (a deferred load leaves the table to the device: no count pass)
   struct BgJoin { std::thread& t; ~BgJoin() { if (t.joinable()) t.join(); } } count_join{count_bg};
   // skip minimizer index + BooPHF (KmerIndex.cpp:1368-1376)
   c.pos = pos1 + dbg_bytes;
@@ -875,6 +891,31 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     ix->utext.assign((g + 15) / 16 + 2, 0);
   }
   tick("unitig text: layout");
+  auto utext_atomic = reinterpret_cast<std::atomic<uint32_t>*>(ix->utext.data());
+  // the unitig's bases into the text (neighbouring unitigs share words: atomic OR)
+  auto write_text = [&](uint64_t u) {
+    const uint64_t g0 = ix->unitig_gpos[u];
+    const uint64_t len = ix->unitig_len[u];
+    const uint64_t sk = u < ix->n_long ? 0 : single_kmer(u);
+    uint32_t acc = 0; uint64_t wi = g0 >> 4;
+    for (uint64_t j = 0; j < len; j++) {
+      const uint64_t g = g0 + j;
+      if ((g >> 4) != wi) { if (acc) utext_atomic[wi].fetch_or(acc, std::memory_order_relaxed); acc = 0; wi = g >> 4; }
+      const uint32_t b = u < ix->n_long ? (uint32_t)((units[u].data[j >> 2] >> ((j & 3) << 1)) & 3)
+                                        : (uint32_t)((sk >> (2 * (k - 1 - (int)j))) & 3);
+      acc |= b << (2 * (g & 15));
+    }
+    if (acc) utext_atomic[wi].fetch_or(acc, std::memory_order_relaxed);
+  };
+  if (deferred) {
+    // the table, its aux arrays, the D-list table and the dummy hit are built by kamd_index_upload on the device (kamd_ixbuild.hip) from
+    // the text, the block tables and the D-list keys: only the text is written here
+    run_parallel([] { return 0; }, [&](uint64_t u, int&) { write_text(u); }, [](int&) {});
+    tick("unitig text");
+    ix->deferred = true; ix->req_layout = want_compact; ix->req_load = compact_load_arg;
+    *out = ix.release();
+    return 0;
+  }
   // (the count pass of the k-mer table has been running since the unitigs were read)
   count_bg.join();
   tick("table: count pass (rest)");
@@ -887,11 +928,10 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     // displacement field can say (14 or 6 buckets): otherwise the wide layout (auto), or a larger table (a sixteenth more buckets) and the
     // count pass again
     auto recount = [&] { fill.resize(nb + 1); fill_atomic = reinterpret_cast<std::atomic<uint32_t>*>(fill.data()); count_pass(); };
-    if (compact && !compact_shifts(k, nb, ix->uec_ec.size(), ix->text_bases, &tag_q, &tag_dsh, &tag_w)) {
-      if (want_compact == KAMD_TABLE_COMPACT) return kamd::fail(-3, "index: the compact k-mer table cannot hold this index (class ids / text positions too wide); use KAMD_TABLE_LAYOUT=wide or auto");
-      compact = false; S = kamd::BUCKET_SLOTS; nb = nb_wide;
-      recount();
-    }
+    const int fit = kamd::ixb::geometry_fit(geo, ix->uec_ec.size(), ix->text_bases);
+    if (fit == kamd::ixb::GEO_FAIL) return kamd::fail(-3, "index: the compact k-mer table cannot hold this index (class ids / text positions too wide); use KAMD_TABLE_LAYOUT=wide or auto");
+    if (fit == kamd::ixb::GEO_RECOUNT) recount();
+    tag_q = geo.tag_q; tag_dsh = geo.tag_dsh; tag_w = geo.tag_w;
     base.resize(nb);
     cursor = 0;
     uint64_t max_disp = 0;
@@ -901,8 +941,7 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
       cursor += fill[b];
       if (fill[b]) max_disp = std::max(max_disp, (cursor - 1) / S - b);
     }
-    if (!compact || max_disp <= (1u << (tag_w - tag_dsh)) - 2u) break;
-    nb += nb / 16 + 1;
+    if (kamd::ixb::geometry_after_scan(geo, max_disp) == kamd::ixb::GEO_OK) break;
     recount();
   }
   ix->n_buckets = nb;
@@ -934,7 +973,6 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
   });
   parallel_range(nb + 1, [&](uint64_t a, uint64_t b) { memset(fill.data() + a, 0, (b - a) * sizeof(uint32_t)); });
   tick("table: layout + allocation");
-  auto utext_atomic = reinterpret_cast<std::atomic<uint32_t>*>(ix->utext.data());
   // stage 1: the k-mer's home bucket (counter + base prefetched); stage 2, RING k-mers later: its slot (table line and aux words
   // prefetched); stage 3, RING k-mers later again: the stores
   struct Pend1 { uint64_t cn, hb, payload; uint32_t gpos, block, dist; };
@@ -986,18 +1024,7 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     };
     if (u < ix->n_long) for_each_kmer_rc(units[u].data, units[u].len, k, place);
     else { const uint64_t v = single_kmer(u); place(0, v, kamd::revcomp_msb(v, k)); }
-    // the unitig's bases into the text (neighbouring unitigs share words: atomic OR)
-    const uint64_t len = ix->unitig_len[u];
-    const uint64_t sk = u < ix->n_long ? 0 : single_kmer(u);
-    uint32_t acc = 0; uint64_t wi = g0 >> 4;
-    for (uint64_t j = 0; j < len; j++) {
-      const uint64_t g = g0 + j;
-      if ((g >> 4) != wi) { if (acc) utext_atomic[wi].fetch_or(acc, std::memory_order_relaxed); acc = 0; wi = g >> 4; }
-      const uint32_t b = u < ix->n_long ? (uint32_t)((units[u].data[j >> 2] >> ((j & 3) << 1)) & 3)
-                                        : (uint32_t)((sk >> (2 * (k - 1 - (int)j))) & 3);
-      acc |= b << (2 * (g & 15));
-    }
-    if (acc) utext_atomic[wi].fetch_or(acc, std::memory_order_relaxed);
+    write_text(u);
   },
                [&](PlaceState& st) {
     for (int i = 0; i < st.na; i++) stage2(st, st.a[(st.ha + i) % RING]);

@@ -13,6 +13,7 @@ struct Options {
   std::vector<std::string> files;
   bool single = false, single_overhang = false, plaintext = false, verbose = false, no_jump = false, do_union = false, share_device = false;
   int gpus = 1;
+  bool index_build_device = false;   // --index-build device: the k-mer table is built by kamd_index_upload on the GPU (kamd_index_load_deferred)
   int table_layout = -1;   // --kmer-table: KAMD_TABLE_WIDE / _COMPACT / _AUTO; -1 = the library's choice (environment, default wide)
   int strand = 0, bootstrap = 0, threads = 1;
   double fld = 0.0, sd = 0.0;
@@ -52,6 +53,8 @@ void usage() {
             << "                              are merged with one RCCL all-reduce + all-gathers, the EM runs partitioned over them\n"
             << "    --kmer-table=wide|compact|auto  layout of the k-mer table in HBM: three 20-byte slots per 64-byte line (wide, default) or\n"
             << "                              four exact 16-byte slots (compact: 27 instead of 43 bytes per k-mer; auto = compact when it fits)\n"
+            << "    --index-build=host|device the k-mer table is built while the index is loaded (host, default) or on the GPU when the index is\n"
+            << "                              uploaded (device: the same table as a one-thread host build); a flattened .kamd file holds its table\n"
             << "    --share-device            with --gpus N: all N ranks on device 0, collectives staged through the host (runs the\n"
             << "                              several-GPU code path on a single-GPU box; for testing)\n";
 }
@@ -200,6 +203,10 @@ int main(int argc, char** argv) {
     else if (take(a, nullptr, "--kmer-table", i, argc, argv, val)) {
       if (!parse_table_layout(val, &opt.table_layout)) { std::cerr << "Error: --kmer-table expects wide, compact or auto" << std::endl; return 1; }
     }
+    else if (take(a, nullptr, "--index-build", i, argc, argv, val)) {
+      if (val != "host" && val != "device") { std::cerr << "Error: --index-build expects host or device" << std::endl; return 1; }
+      opt.index_build_device = val == "device";
+    }
     else if (a == "--bias" || a == "--fusion" || a == "--pseudobam" || a == "--genomebam" || a == "--long" || a == "-p" || a == "--priors" ||
              a == "-g" || a == "--gtf" || a == "-c" || a == "--chromosomes" || a == "--dfk-onlist" ||
              a == "-P" || a == "--platform" || a == "-N" || a == "--numReads") {
@@ -258,7 +265,7 @@ int main(int argc, char** argv) {
   int load_rc = 0; std::string load_err;
   const int load_threads = std::min(opt.threads, effective_cpus());
   std::thread load_early([&] {
-    auto load = [&](const std::string& p) { return opt.table_layout < 0 ? kamd_index_load(p.c_str(), load_threads, &idx) : kamd_index_load_layout(p.c_str(), load_threads, opt.table_layout, 0.0, &idx); };
+    auto load = [&](const std::string& p) { return opt.index_build_device ? kamd_index_load_deferred(p.c_str(), load_threads, opt.table_layout, 0.0, &idx) : opt.table_layout < 0 ? kamd_index_load(p.c_str(), load_threads, &idx) : kamd_index_load_layout(p.c_str(), load_threads, opt.table_layout, 0.0, &idx); };
     load_rc = load(index_path);
     if (load_rc && index_path != opt.index) {   // a flattened file picked up beside the index that does not load (another format version, damaged): the index itself
       std::cerr << "[index] " << index_path << " ignored: " << kamd_last_error() << std::endl;
@@ -329,8 +336,12 @@ int main(int argc, char** argv) {
     if (opt.bootstrap > 0 && n_gpus == 1 && kamd_ec_track_order(ctx, 1) != 0) { done(-1, kamd_last_error()); return; }
     index_ready_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     if (index_path != opt.index) std::cerr << "[index] using the flattened tables of " << index_path << std::endl;
-    if (opt.verbose) std::cerr << "[index] k-mer table: " << (v.table_layout ? "compact" : "wide") << " layout, " << v.slots_per_bucket << " slots per 64-byte line, "
-                               << (v.n_buckets + v.pad_buckets) * 64 / 1000000 << " MB, load " << (double)v.n_kmers / (double)(v.n_buckets * v.slots_per_bucket) << std::endl;
+    kamd_table_info ti{};
+    if (kamd_ctx_table_info(ctx, &ti) != 0) { done(-1, kamd_last_error()); return; }
+    if (opt.verbose) std::cerr << "[index] k-mer table: " << (ti.table_layout ? "compact" : "wide") << " layout, " << ti.slots_per_bucket << " slots per 64-byte line, "
+                               << (ti.n_buckets + ti.pad_buckets) * 64 / 1000000 << " MB, load " << (double)v.n_kmers / (double)(ti.n_buckets * ti.slots_per_bucket) << std::endl;
+    if (opt.verbose && ti.built_on_device) std::cerr << "[index] k-mer table built on the device in " << ti.build_ms << " ms (count + scan " << ti.build_count_ms << ", place " << ti.build_place_ms
+                               << ", order " << ti.build_order_ms << ", fill " << ti.build_fill_ms << ", D-list " << ti.build_dlist_ms << ")" << std::endl;
     if (opt.verbose) std::cerr << "[timing] index file read + flattened in " << index_load_s << " s, on the device after " << index_ready_s << " s" << std::endl;
     done(1, "");
   });

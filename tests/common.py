@@ -60,7 +60,8 @@ def parse_variant(extra):
 
 def load_expected(name, variant):
     res = {"nproc": 0, "ecs": {}, "flens": np.zeros(MAX_FRAG_LEN, np.uint32), "tr": [], "bs": {}}
-    with open(os.path.join(case_dir(name), f"expected_{variant}.txt")) as f:
+    path = os.path.join(case_dir(name), f"expected_{variant}.txt")
+    with (open(path) if os.path.exists(path) else gzip.open(path + ".gz", "rt")) as f:     # bigsets_pe commits them gzipped
         for line in f:
             t = line.split()
             if t[0] == "NPROC":

@@ -17,6 +17,8 @@
  *       MasterProcessor::update / processReads   src/ProcessReads.cpp:424-499,323-334 -> kamd_ec_finalize; over several GPUs kamd_ec_allreduce
  *                                                (kamd_comm: RCCL inside the library) + kamd_em_run_comm
  *       FastqSequenceReader::fetchSequences      src/ProcessReads.cpp:3128-3267   -> kamd_pack_reads (2-bit packing of a parsed batch)
+ *       BUSProcessor::processBuffer, --aa branch  src/ProcessReads.cpp:1633-1726   -> kamd_pseudoalign_aa (translated search: six comma-free
+ *       (nn_to_cfc src/KmerIndex.cpp:16-138, MinCollector::intersectKmersCFC src/MinCollector.cpp:44-119)   frames per read, kamd_cfc_frames)
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -102,7 +104,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 6
+#define KAMD_ABI_VERSION 7
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -470,6 +472,31 @@ int kamd_bootstrap_batch(kamd_ctx*, const uint64_t* seeds, int32_t n_rep, const 
                          int32_t* rounds);
 /* seeds[b] = std::mt19937_64(seed)() for b = 0..n-1 (src/main.cpp:2746-2752) */
 void kamd_bootstrap_seeds(uint64_t seed, int32_t n, uint64_t* seeds);
+
+/* ---- translated search (`kallisto bus --aa`, src/ProcessReads.cpp:1633-1726) ----
+ * Nucleotide reads against an index built from amino-acid sequences (`kallisto index --aa`, loaded like any other index).  Every read is
+ * translated in six reading frames into the comma-free code (frame f < 3: s + f; f >= 3: rc(s) + (f - 3); every complete codon becomes
+ * three bases, a stop codon or a codon with a non-ACGT base three masked ones), every frame goes through KmerIndex::match with
+ * partial = false, the frame's sets are intersected under dfk_onlist (a target that is not on-list -- a D-list pseudo-target -- is sticky),
+ * and MinCollector::intersectKmersCFC picks the read's class: a frame with an off-list member rejects the read, otherwise the first
+ * frame with the smallest non-empty set wins.  Single-end only, as in the reference; --union and --no-jump do not exist here.
+ *
+ * kamd_cfc_frames: the six frame records of every read, in the layout of the input (kamd_packed_record_words(max_len) words per record,
+ * record 6 * r + f = frame f of read r; d_out_len[6 * r + f] = translated length).  d_out_words: 6 * n_reads records, d_out_len: 6 * n_reads.
+ * kamd_pseudoalign_aa: one batch of single-end reads, accumulated into the context's EC state like kamd_pseudoalign (kamd_ec_finalize,
+ * kamd_ec_download, the tuple export / replace and kamd_ec_allreduce work unchanged).  Not with kamd_ec_track_order. */
+int kamd_cfc_frames(kamd_ctx*, const uint32_t* d_words, const uint16_t* d_len, uint64_t n_reads, int32_t max_len, uint32_t* d_out_words,
+                    uint16_t* d_out_len);
+int kamd_pseudoalign_aa(kamd_ctx*, const uint32_t* d_words, const uint16_t* d_len, uint64_t n_reads, int32_t max_len);
+typedef struct {
+  uint64_t n_processed;          /* since kamd_ec_reset: reads given to kamd_pseudoalign_aa */
+  uint64_t n_rejected_offlist;   /* ... rejected because a frame's set holds an off-list target (the host genome of the D-list) */
+  uint64_t n_all_empty;          /* ... whose six frames all came out empty */
+  uint64_t n_frame_clashes;      /* MinCollector::cardinality_clashes: later frames as good as the winner at the moment they are visited */
+  uint64_t n_winner[6];          /* pseudoaligned reads by winning frame */
+  float last_translate_ms, last_match_ms;   /* the two kernels of the last batch */
+} kamd_aa_stats;
+int kamd_aa_stats_get(kamd_ctx*, kamd_aa_stats* out);
 
 /* ---- the quant flow in one call (ProcessReads -> fragment-length model -> EMAlgorithm::run, src/main.cpp:2654-2730) ----
  * For a caller whose reads already sit in HBM in the packed layout: the batches are pseudoaligned in order (fragment-length sample:

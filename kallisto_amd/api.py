@@ -59,7 +59,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 6   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 7   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -74,6 +74,12 @@ class _Profile(C.Structure):
                 ("last_em_giant_tr", C.c_uint64), ("last_em_giant_chunks", C.c_uint32), ("last_em_graph_fallback", C.c_int32),
                 ("last_em_plan_ms", C.c_float), ("n_overflow_items", C.c_uint64), ("overflow_ms", C.c_float),
                 ("last_merge_ms", C.c_float), ("em_collective_ms", C.c_float), ("em_collectives", C.c_uint32), ("n_overflow_second_pass", C.c_uint64), ("last_em_giant_pieces", C.c_uint64)]
+
+
+class _AaStats(C.Structure):
+    """kamd_aa_stats: what the translated search did with the reads since the last reset."""
+    _fields_ = [("n_processed", C.c_uint64), ("n_rejected_offlist", C.c_uint64), ("n_all_empty", C.c_uint64), ("n_frame_clashes", C.c_uint64),
+                ("n_winner", C.c_uint64 * 6), ("last_translate_ms", C.c_float), ("last_match_ms", C.c_float)]
 
 
 class _TableInfo(C.Structure):
@@ -175,6 +181,9 @@ _SYMBOLS = {
                                  C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "kamd_bootstrap_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "kamd_bootstrap_seeds": (None, [C.c_uint64, C.c_int32, C.c_void_p]),
+    "kamd_cfc_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "kamd_pseudoalign_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]),
+    "kamd_aa_stats_get": (C.c_int, [C.c_void_p, C.POINTER(_AaStats)]),
     "kamd_quant_batches": (C.c_int, [C.c_void_p, C.POINTER(QuantOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(_QuantOut)]),
     "kamd_mean_frag_lens_trunc": (None, [C.c_void_p, C.c_void_p]),
     "kamd_trunc_gaussian_fld": (None, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]),
@@ -472,6 +481,29 @@ class Context:
     def pseudoalign(self, opts: QuantOpts, words, lens, n_items: int, max_len: int):
         _check(load_library().kamd_pseudoalign(self._h, C.byref(opts), words.data_ptr(), lens.data_ptr(), n_items, max_len),
                "kamd_pseudoalign")
+
+    # ---- translated search (bus --aa) ----
+    def cfc_frames(self, words, lens, n_reads: int, max_len: int):
+        """kamd_cfc_frames: the six comma-free frames of every read as packed records (record 6 * r + f, the layout of the input) and
+        their translated lengths.  Returns (words int32 [6 * n_reads * packed_record_words(max_len)], lens int16 [6 * n_reads])."""
+        torch = self.torch
+        rec = packed_record_words(max_len)
+        out_w = torch.zeros(max(6 * n_reads * rec, 1), dtype=torch.int32, device=f"cuda:{self.device}")
+        out_l = torch.zeros(max(6 * n_reads, 1), dtype=torch.int16, device=f"cuda:{self.device}")
+        _check(load_library().kamd_cfc_frames(self._h, words.data_ptr(), lens.data_ptr(), n_reads, max_len, out_w.data_ptr(), out_l.data_ptr()),
+               "kamd_cfc_frames")
+        return out_w[:6 * n_reads * rec], out_l[:6 * n_reads]
+
+    def pseudoalign_aa(self, words, lens, n_reads: int, max_len: int):
+        """kamd_pseudoalign_aa: one batch of single-end reads against an amino-acid index, accumulated into the context's EC state."""
+        _check(load_library().kamd_pseudoalign_aa(self._h, words.data_ptr(), lens.data_ptr(), n_reads, max_len), "kamd_pseudoalign_aa")
+
+    def aa_stats(self) -> dict:
+        s = _AaStats()
+        _check(load_library().kamd_aa_stats_get(self._h, C.byref(s)), "kamd_aa_stats_get")
+        return {"n_processed": int(s.n_processed), "n_rejected_offlist": int(s.n_rejected_offlist), "n_all_empty": int(s.n_all_empty),
+                "n_frame_clashes": int(s.n_frame_clashes), "n_winner": [int(x) for x in s.n_winner],
+                "translate_ms": float(s.last_translate_ms), "match_ms": float(s.last_match_ms)}
 
     def fld_prefetch(self, opts: QuantOpts, words, lens, n_items: int, max_len: int):
         """Start the FLD kernel for the first prefix of a batch on a side stream (kamd_fld_prefetch); fld_from_batch on the same

@@ -4,6 +4,8 @@
 //                                        BUSProcessor::processBuffer src/ProcessReads.cpp:1380-1832 in its bulk form: every file /
 //                                        pair of files is a sample, barcode = sample, no UMI, the same match + intersectKmers as
 //                                        quant, no position filter (`single_overhang = true`, :762), per-sample fragment lengths)
+//   kallisto_amd_quant bus --aa ...      translated search (src/ProcessReads.cpp:1633-1726): nucleotide reads against an index of amino-acid
+//                                        sequences, six comma-free frames per read (kamd_pseudoalign_aa); single-end only
 //   kallisto_amd_quant quant-tcc ...     `kallisto quant-tcc` (src/main.cpp:2802-3220): EMAlgorithm::run per row of a
 //                                        transcript-compatibility-count matrix over the classes of an EC file
 //
@@ -48,6 +50,8 @@ void usage_bus() {
             << "    --paired                  Treat reads as paired\n"
             << "    --fr-stranded / --rf-stranded / --unstranded\n"
             << "    --union, --no-jump        As in quant\n"
+            << "    --aa                      Align to index generated from a FASTA-file containing amino acid sequences: every read is\n"
+            << "                              translated in six reading frames (single-end only; not with --union / --no-jump)\n"
             << "-t, --threads=INT             Host threads (default: 1)\n"
             << "    --index-build=host|device As in quant: where the k-mer table is built (default: host)\n"
             << "    --bus-per-read            output.bus with one record per pseudoaligned read (count 1), as the reference writes it; by default\n"
@@ -72,7 +76,7 @@ int bus_main(int argc, char** argv) {
   if (argc == 2) { usage_bus(); return 0; }
   std::string index, output, technology, batch_file, val;
   std::vector<std::string> files;
-  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false;
+  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false, aa = false;
   int strand = 0, threads = 1;
   uint64_t batch = 4u << 20;
   for (int i = 2; i < argc; i++) {
@@ -94,10 +98,11 @@ int bus_main(int argc, char** argv) {
     else if (a == "--union") do_union = true;
     else if (a == "--no-jump") no_jump = true;
     else if (a == "--bus-per-read") per_read = true;
+    else if (a == "--aa") aa = true;
     else if (a == "--verbose") verbose = true;
     else if (a == "-l" || a == "--list" || a == "-b" || a == "--bam" || a == "-n" || a == "--num" || a == "--genomebam" || a == "-g" || a == "--gtf" ||
              a == "-c" || a == "--chromosomes" || a == "-T" || a == "--tag" || a == "--long" || a == "-P" || a == "--platform" || a == "-r" ||
-             a == "--threshold" || a == "--unmapped" || a == "--aa" || a == "--inleaved" || a == "-N" || a == "--numReads" ||
+             a == "--threshold" || a == "--unmapped" || a == "--inleaved" || a == "-N" || a == "--numReads" ||
              a == "--batch-barcodes" || a == "--dfk-onlist") {
       std::cerr << "Error: option " << a << " is outside the GPU bulk path; use the reference kallisto for it" << std::endl; return 1;
     } else if (!a.empty() && a[0] == '-') { std::cerr << "Error: unknown option " << a << std::endl; usage_bus(); return 1; }
@@ -107,6 +112,12 @@ int bus_main(int argc, char** argv) {
   bool ok = true;
   struct stat st;
   std::cerr << std::endl;
+  if (aa) {   // src/main.cpp:758-770, 969-976
+    if (paired) std::cerr << "[bus] --paired ignored; --aa only supports single-end reads" << std::endl;
+    paired = false;
+    if (do_union) { std::cerr << "--union is not compatible with this mode" << std::endl; ok = false; }
+    if (no_jump) { std::cerr << "--no-jump is not compatible with this mode" << std::endl; ok = false; }
+  }
   if (index.empty()) { std::cerr << "Error: kallisto index file missing" << std::endl; ok = false; }
   else if (stat(index.c_str(), &st) != 0) { std::cerr << "Error: kallisto index file not found " << index << std::endl; ok = false; }
   if (output.empty()) { std::cerr << "Error: need to specify output directory " << output << std::endl; ok = false; }
@@ -147,6 +158,7 @@ int bus_main(int argc, char** argv) {
         if (id.empty() || id[0] == '#') continue;
         ss >> f1 >> f2;
         if (first) { paired = !f2.empty(); first = false; }
+        if (aa && paired) { std::cerr << "Error: --aa only supports single-end reads (one file per line of the batch file)" << std::endl; ok = false; break; }
         if (f1.empty() || (paired && f2.empty()) || (!paired && !f2.empty())) { std::cerr << "Error: batch file malformatted" << std::endl; ok = false; break; }
         std::vector<std::string> fs{f1};
         if (paired) fs.push_back(f2);
@@ -194,7 +206,7 @@ int bus_main(int argc, char** argv) {
   std::vector<const std::vector<uint32_t>*> ec_sets;
   std::map<uint64_t, std::map<int32_t, uint64_t>> per_barcode;          // barcode -> class -> reads
   std::vector<std::vector<uint32_t>> sample_flens(batch_ids.size(), std::vector<uint32_t>(KAMD_MAX_FRAG_LEN, 0));
-  uint64_t n_processed = 0, num_pseudoaligned = 0, num_unique = 0;
+  uint64_t n_processed = 0, num_pseudoaligned = 0, num_unique = 0, n_frame_clashes = 0;
   double pack_s = 0.0;
   // one pipeline for all samples (text rings and buffers are allocated once); the sample under way is behind these two
   uint32_t* flens = nullptr;
@@ -202,6 +214,11 @@ int bus_main(int argc, char** argv) {
   auto run_batch = [&](int, PackedBatch& b, std::string& err) -> int {
     const bool want_fld = paired && fld_used < 10000;
     int rc = 0;
+    if (aa) {
+      rc = kamd_pseudoalign_aa(ctx, b.d_words, b.d_len, b.n_items, b.max_len);
+      if (rc) err = kamd_last_error();
+      return rc;
+    }
     if (want_fld) rc = kamd_fld_prefetch(ctx, &qo, b.d_words, b.d_len, b.n_items, b.max_len);
     if (!rc) rc = kamd_pseudoalign(ctx, &qo, b.d_words, b.d_len, b.n_items, b.max_len);
     if (!rc && want_fld) rc = kamd_fld_from_batch(ctx, &qo, b.d_words, b.d_len, b.n_items, b.max_len, flens, &fld_used);
@@ -220,6 +237,7 @@ int bus_main(int argc, char** argv) {
       pipe.finish();
       if (pipe.failed()) { std::cerr << "Error: " << pipe.error() << std::endl; return 1; }
     }
+    if (aa) { kamd_aa_stats as; KX(kamd_aa_stats_get(ctx, &as)); n_frame_clashes += as.n_frame_clashes; }   // (per sample: kamd_ec_reset clears them)
     kamd_ec_result ec;
     KX(kamd_ec_finalize(ctx, &ec));
     std::vector<uint64_t> ec_off(ec.n_ecs + 1); std::vector<uint32_t> ec_ids(std::max<uint64_t>(ec.nnz, 1)), counts(std::max<uint64_t>(ec.n_ecs, 1));
@@ -280,7 +298,8 @@ int bus_main(int argc, char** argv) {
       of << "\n";
     }
   }
-  write_run_info(output + "/run_info.json", n_on, 0, n_processed, num_pseudoaligned, num_unique, v.k, start_time, call);
+  write_run_info(output + "/run_info.json", n_on, 0, n_processed, num_pseudoaligned, num_unique, v.k, start_time, call,
+                 aa ? std::to_string(n_frame_clashes) : std::string());
   std::cerr << std::endl;
   kamd_ctx_destroy(ctx);
   kamd_index_free(idx);

@@ -155,6 +155,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   for (hipEvent_t e : c->al_ev_chunk) if (e) (void)hipEventDestroy(e);
   if (c->ev_fin0) (void)hipEventDestroy(c->ev_fin0);
   if (c->ev_fin1) (void)hipEventDestroy(c->ev_fin1);
+  for (hipEvent_t e : c->aa_ev) if (e) (void)hipEventDestroy(e);
   if (c->ev_ab0) (void)hipEventDestroy(c->ev_ab0);
   if (c->ev_ab1) (void)hipEventDestroy(c->ev_ab1);
   if (c->em_stream) (void)hipStreamDestroy(c->em_stream);
@@ -190,7 +191,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
                   &c->em_state, &c->em_cn, &c->em_colcnt, &c->em_coloff, &c->em_colrow,
                   &c->em_segoff, &c->em_segt, &c->em_partial, &c->em_a0, &c->em_a1, &c->em_single, &c->em_actflag, &c->em_actpos, &c->em_active, &c->pt_label, &c->pt_flag, &c->pt_len,
                   &c->pt_rowpos, &c->pt_nnzpos, &c->pt_off, &c->pt_ids, &c->pt_counts, &c->pt_wcounts, &c->pt_hist, &c->pt_ck_alpha,
-                  &c->pt_ck_a, &c->fq_tiles, &c->fq_nlpos[0], &c->fq_nlpos[1], &c->fq_recs, &c->fq_res, &c->fq_words, &c->fq_len})
+                  &c->pt_ck_a, &c->fq_tiles, &c->fq_nlpos[0], &c->fq_nlpos[1], &c->fq_recs, &c->fq_res, &c->fq_words, &c->fq_len, &c->aa_frames, &c->aa_flen, &c->aa_scratch, &c->aa_offlist, &c->aa_ctr})
     b->release();
   delete c;
 }
@@ -288,6 +289,7 @@ extern "C" int kamd_index_upload(kamd_ctx* c, const kamd_index* hix) {
     ti.dummy_slot = v.dummy_slot; ti.dummy_uec = v.dummy_uec; ti.dummy_strand = v.dummy_strand;
   }
   c->tinfo = ti;
+  c->aa_ready = false; memset(&c->aa_stats, 0, sizeof c->aa_stats);
   c->ix = d; c->has_index = true; c->n_ecs = v.n_ecs; c->n_targets = v.n_targets;
   if (int rc = c->dense.ensure(std::max<u64>(v.n_ecs, 1) * sizeof(u32), 0, c->stream)) return rc;
   HIPC(hipMemsetAsync(c->dense.p, 0, std::max<u64>(v.n_ecs, 1) * sizeof(u32), c->stream));
@@ -311,6 +313,7 @@ extern "C" int kamd_ec_reset(kamd_ctx* c) {
   if (int rc = tuples_clear(c)) return rc;
   HIPC(hipMemsetAsync(c->stats_a.p, 0, sizeof(DevStatsA), c->stream));
   c->had_overflow_items = false;
+  memset(&c->aa_stats, 0, sizeof c->aa_stats);
   c->fq_batch_reads = 0; c->fq_batch_max_len = 0; c->fq_batch_files = 0;   // (units parsed but never packed belong to the abandoned run)
   return push_state(c);
 }

@@ -6,6 +6,7 @@
 //   kamd_io.hip      FASTQ text in HBM -> packed reads
 //   kamd_ctx.hip     context, index upload, tuning, diagnostics, communicators and what runs over them
 //   kamd_ixbuild.hip the k-mer table built on the device (upload of an index loaded with kamd_index_load_deferred), kamd_ctx_table_*
+//   kamd_aa.hip      translated search: the six comma-free frames of a read, match and frame rule (kamd_cfc_frames, kamd_pseudoalign_aa); per-item logic in kamd_aa.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -306,6 +307,12 @@ struct kamd_ctx {
   bool had_overflow_items = false;   // some item went through the overflow kernel (tuples of more than TUPLE_CAP sets may exist)
   int n_cus = 0, last_em_k = 0; unsigned last_em_grid = 0, last_em_lds = 0;
   uint64_t last_em_iters = 0, last_em_nnz = 0, last_em_nnz_multi = 0, last_em_nseg = 0, last_em_necs = 0;
+  // translated search (kamd_aa.hip): the batch's frame records and their translated lengths, the class lists of the resident lanes, one "has an off-list
+  // member" byte per index set (computed on the first call after an upload), the counters of a call; what kamd_aa_stats_get reports
+  DBuf aa_frames, aa_flen, aa_scratch, aa_offlist, aa_ctr;
+  bool aa_ready = false;
+  kamd_aa_stats aa_stats{};
+  hipEvent_t aa_ev[3] = {nullptr, nullptr, nullptr};
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 

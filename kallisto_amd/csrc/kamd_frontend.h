@@ -645,7 +645,8 @@ inline int feed_files(const std::vector<std::string>& files, bool paired, uint64
 
 // run_info.json (plaintext_aux, PlaintextWriter.cpp:140-197)
 inline void write_run_info(const std::string& path, uint64_t n_targets, int n_bootstraps, uint64_t n_processed, uint64_t n_pseudoaligned,
-                           uint64_t n_unique, int k, const std::string& start_time, const std::string& call) {
+                           uint64_t n_unique, int k, const std::string& start_time, const std::string& call,
+                           const std::string& frame_clashes = "") {   // (bus --aa: MinCollector::cardinality_clashes, src/PlaintextWriter.cpp:190-192)
   double p_uniq = 0.0, p_aln = 0.0;
   if (n_processed > 0) { p_uniq = 100.0 * (double)n_unique / (double)n_processed; p_aln = 100.0 * (double)n_pseudoaligned / (double)n_processed; }
   std::stringstream s1, s2; s1 << std::fixed << std::setprecision(1) << p_uniq; s2 << std::fixed << std::setprecision(1) << p_aln;
@@ -662,8 +663,9 @@ inline void write_run_info(const std::string& path, uint64_t n_targets, int n_bo
      << to_json("index_version", "13", false) << std::endl
      << to_json("k-mer length", std::to_string(k), false) << std::endl
      << to_json("start_time", start_time, true) << std::endl
-     << to_json("call", call, true, false) << std::endl
-     << "}" << std::endl;
+     << to_json("call", call, true, frame_clashes.empty() ? false : true) << std::endl;
+  if (!frame_clashes.empty()) of << to_json("n_frame_clashes", frame_clashes, false, false) << std::endl;
+  of << "}" << std::endl;
 }
 
 inline std::string now_string() {

@@ -85,6 +85,21 @@ typedef struct {
    * KAMD_TABLE_LAYOUT=wide (default) | compact | auto (compact when its fields fit), KAMD_TABLE_LOAD = load factor of the compact
    * table (default 0.6; the wide one is built at 0.5).  slot index = b * slots_per_bucket + j. */
   uint32_t table_layout, slots_per_bucket, tag_q, tag_dsh, tag_w;
+  /* Shades (kallisto 0.51's allele-aware classes; src/KmerIndex.cpp:236-244, 1505-1518, src/MinCollector.cpp:160-218, 425-496): a target whose
+   * name holds "_shade_" is a shade of the first earlier target named by the text before it, its colour.  n_shades != 0 switches the class rule:
+   * the sets are intersected without their shades (their cores), and every shade of any of the item's sets whose colour survived is united
+   * back in; match() runs with partial = false and the strand filter per hit, as with --union.  The pointers below are NULL when n_shades == 0;
+   * a flattened file (kamd_index_save) carries the tables.  An index in which a set holds a shade without its colour is refused too (-3): the
+   * reference's builder never writes one, and the rule above leans on it.
+   * An index with a shade that has no base target before it is refused by kamd_index_load (-3). */
+  uint64_t n_shades;
+  const uint32_t* shade_colour;   /* [n_targets] base target of a shade, 0xFFFFFFFF for every other target */
+  const uint64_t* core_off;       /* [n_ecs + 1]: per transcript set its members that are no shades (ec_off / ec_ids stay the full sets: */
+  const uint32_t* core_ids;       /* [core_nnz]    the positional tables are parallel to those) */
+  uint64_t core_nnz;
+  const uint64_t* shade_off;      /* [n_ecs + 1]: ... and its members that are */
+  const uint32_t* shade_ids;      /* [shade_nnz] */
+  uint64_t shade_nnz;
 } kamd_index_view;
 
 typedef struct {
@@ -104,7 +119,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 7
+#define KAMD_ABI_VERSION 8
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -138,6 +153,11 @@ int kamd_flat_index_matches(const char* flat_path, const char* index_path);
 void kamd_index_free(kamd_index*);
 int kamd_index_get_view(const kamd_index*, kamd_index_view* out);
 const char* kamd_index_target_name(const kamd_index*, uint64_t i);
+/* Options this index cannot run with: 0 = fine, -5 = refused (kamd_last_error says why).  An index with shades refuses the positional
+ * fragment-length filter -- fld != 0 without single_overhang: --single without --single-overhang, and paired reads with -l / -s, whose orphan
+ * mates reach the filter -- because the reference itself aborts there (findPosition is asked about a shade that is not in the first mapping
+ * k-mer's set: "Index not present in SparseVector").  kamd_pseudoalign applies the same test; a front-end asks before it uploads. */
+int kamd_index_check_opts(const kamd_index*, const kamd_quant_opts*);
 
 /* ---- context ---- */
 /* Tuning knobs: which of the equivalent kernels / EM forms run and how they are shaped.  None of them changes a result.
@@ -265,7 +285,10 @@ int kamd_fastq_unit_pack(kamd_ctx*, const char* const* d_text, const uint64_t* n
  * n_items = pairs (paired) or reads (single).  Accumulates into the context's EC state; call kamd_ec_finalize after
  * the last batch.  The EC state is bounded by the number of DISTINCT classes, like MinCollector's (src/MinCollector.cpp:251-269): a
  * dense count vector over the index's transcript sets plus a table of the distinct tuples of set ids seen so far; the per-item
- * records of a batch are recycled when the call returns. */
+ * records of a batch are recycled when the call returns.
+ * An index with shades (kamd_index_view::n_shades != 0): the EC state is the same -- dense counts and tuples of set ids --, and kamd_ec_finalize
+ * resolves a tuple as the intersection of its sets' cores with every shade of any of its sets united back in whose colour is in it; match() runs
+ * with partial = false and a strand option filters per hit; -5 for fld != 0 without single_overhang (kamd_index_check_opts). */
 int kamd_pseudoalign(kamd_ctx*, const kamd_quant_opts*, const uint32_t* d_words, const uint16_t* d_len, uint64_t n_items,
                      int32_t max_len);
 /* fragment-length histogram from the first 10000 qualifying pairs in input order (src/ProcessReads.cpp:981-1017,

@@ -36,7 +36,11 @@ class _View(C.Structure):
                 [("onlist_words", C.c_uint64), ("dtable", C.c_void_p), ("n_dbuckets", C.c_uint64), ("dpad_buckets", C.c_uint64),
                  ("dummy_slot", C.c_uint64), ("dummy_uec", C.c_uint32), ("dummy_strand", C.c_uint32),
                  ("utext", C.c_void_p), ("utext_words", C.c_uint64), ("text_bases", C.c_uint64), ("unitig_gpos", C.c_void_p)] +
-                [(n, C.c_uint32) for n in ("table_layout", "slots_per_bucket", "tag_q", "tag_dsh", "tag_w")])
+                [(n, C.c_uint32) for n in ("table_layout", "slots_per_bucket", "tag_q", "tag_dsh", "tag_w")] +
+                # the shade tables: their addresses as integers, 0 when the index has no shade (n_shades == 0)
+                [("n_shades", C.c_uint64), ("shade_colour", C.c_size_t),
+                 ("core_off", C.c_size_t), ("core_ids", C.c_size_t), ("core_nnz", C.c_uint64),
+                 ("shade_off", C.c_size_t), ("shade_ids", C.c_size_t), ("shade_nnz", C.c_uint64)])
 
 
 class QuantOpts(C.Structure):
@@ -59,7 +63,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 7   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 8   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -123,6 +127,7 @@ _SYMBOLS = {
     "kamd_index_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kamd_index_get_view": (C.c_int, [C.c_void_p, C.POINTER(_View)]),
     "kamd_index_target_name": (C.c_char_p, [C.c_void_p, C.c_uint64]),
+    "kamd_index_check_opts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kamd_ctx_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "kamd_ctx_destroy": (None, [C.c_void_p]),
     "kamd_ctx_tune": (C.c_int, [C.c_void_p, C.POINTER(Tuning)]),
@@ -281,6 +286,10 @@ class Index:
         self.num_kmers, self.num_unitigs, self.num_blocks = v.n_kmers, v.n_unitigs, v.n_blocks
         self.num_ecs, self.num_targets = v.n_ecs, v.n_targets
         self.target_lens = _np(v.target_lens, v.n_targets, np.int32).copy()
+        # shades (targets named <base>_shade_<variant>): their number, and per target its base target (0xFFFFFFFF for a target that is no shade)
+        self.n_shades = int(v.n_shades)
+        self.shade_colour = (_np(v.shade_colour, v.n_targets, np.uint32).copy() if self.n_shades
+                             else np.full(int(v.n_targets), 0xFFFFFFFF, np.uint32))
 
     @property
     def handle(self):
@@ -294,6 +303,19 @@ class Index:
         """(ec_off, ec_ids) of the de-duplicated index transcript sets (host views)."""
         v = self.view
         return _np(v.ec_off, v.n_ecs + 1, np.uint64), _np(v.ec_ids, v.ec_nnz, np.uint32)
+
+    def check_opts(self, opts: "QuantOpts"):
+        """kamd_index_check_opts: raises for options this index cannot run with (an index with shades and -l / -s without --single-overhang)"""
+        _check(load_library().kamd_index_check_opts(self._h, C.byref(opts)), "kamd_index_check_opts")
+
+    def shade_sets(self):
+        """(core_off, core_ids, shade_off, shade_ids): every transcript set split into its members that are no shades and those that are
+        (host views; four empty arrays when the index has no shade)."""
+        v = self.view
+        if not self.n_shades:
+            return tuple(np.zeros(0, t) for t in (np.uint64, np.uint32, np.uint64, np.uint32))
+        return (_np(v.core_off, v.n_ecs + 1, np.uint64), _np(v.core_ids, v.core_nnz, np.uint32),
+                _np(v.shade_off, v.n_ecs + 1, np.uint64), _np(v.shade_ids, v.shade_nnz, np.uint32))
 
     def save(self, path: str):
         """kamd_index_save: the flattened tables as a file that Index(path) / kamd_index_load reads back without rebuilding them."""

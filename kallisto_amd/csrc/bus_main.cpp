@@ -189,6 +189,10 @@ int bus_main(int argc, char** argv) {
   else KX(kamd_index_load(index.c_str(), threads, &idx));
   kamd_index_view v; KX(kamd_index_get_view(idx, &v));
   std::cerr << "\n[index] k-mer length: " << v.k << "\n[index] number of targets: " << v.n_targets << "\n[index] number of k-mers: " << v.n_kmers << std::endl;
+  if (v.n_shades) {   // (KmerIndex.cpp:1539-1542)
+    std::cerr << "[build] number of shades: " << v.n_shades << std::endl;
+    if (aa) { std::cerr << "Error: --aa is not defined for an index with shades" << std::endl; return 1; }
+  }
   kamd_ctx* ctx = nullptr;
   KX(kamd_ctx_create(0, nullptr, &ctx));
   KX(kamd_index_upload(ctx, idx));

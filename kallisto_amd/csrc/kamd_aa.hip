@@ -157,6 +157,7 @@ extern "C" int kamd_pseudoalign_aa(kamd_ctx* c, const uint32_t* d_words, const u
   if (int rc = aa_check_batch(c, d_words, d_len, max_len, "kamd_pseudoalign_aa")) return rc;
   if (!c->has_index) return kamd::fail(-1, "kamd_pseudoalign_aa: no index uploaded");
   if (c->track_order) return kamd::fail(-5, "kamd_pseudoalign_aa: not with kamd_ec_track_order");
+  if (c->ix.n_shades) return kamd::fail(-5, "kamd_pseudoalign_aa: the translated search is not defined for an index with shades");
   if (n_reads == 0) return 0;
   HIPC(hipSetDevice(c->device));
   if (c->ov_side_pending) { HIPC(hipStreamSynchronize(c->ov_stream)); c->ov_side_pending = false; }

@@ -684,6 +684,73 @@ KAMD_HD uint64_t set_size_bound(const SetTables& st, const uint32_t* e, int n, b
   return union_mode ? sum : (n ? mn : 0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Shades (allele-aware classes; MinCollector.cpp:160-218, 425-496 with index.use_shade).  A target named <base>_shade_<variant> is a
+// shade, <base> its colour.  On an index with shades
+//   * intersectECs (and the u1 & u2 of intersectKmers) work on the sets WITHOUT their shades, their cores; the index builder puts the
+//     colour into every set that gets a shade, so a set with an empty core is an empty set and the emptiness rules do not change;
+//   * for a non-empty result r, S = the shades of ALL sets either mate's hits carried (unionECs keeps them), and
+//     r |= {s in S : colour(s) in r}.  With --union and one mate, r = u1 already holds u1's shades: their colours are in u1, so the same
+//     expression gives them.
+// The result is enumerated in increasing target id -- shades interleave with the other members -- without materialising r: membership of
+// a colour in r is decided from the sets themselves.
+// ---------------------------------------------------------------------------------------------------------------
+struct ShadeTables { const uint64_t* core_off; const uint32_t* core_ids; const uint64_t* shade_off; const uint32_t* shade_ids; const uint32_t* colour; };
+static const uint32_t NO_TARGET = 0xFFFFFFFFu;
+// first position of a sorted list with ids[pos] >= x
+KAMD_HD uint64_t sorted_lower_bound(const uint32_t* ids, uint64_t n, uint32_t x) {
+  uint64_t lo = 0, hi = n;
+  while (lo < hi) { const uint64_t mid = (lo + hi) >> 1; if (ids[mid] < x) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+// is x (no shade) a member of the item's set before the shades are put back: in every core, or with --union in some core of each mate that has sets
+KAMD_HD bool core_result_has(const ShadeTables& sh, const EcList& ecs, bool union_mode, uint32_t x) {
+  bool has1 = false, has2 = false, in1 = false, in2 = false;
+  for (int j = 0; j < ecs.n; j++) {
+    const uint32_t e = ecs.e[j] & EC_ID_MASK;
+    const uint32_t* ids = sh.core_ids + sh.core_off[e];
+    const uint64_t n = sh.core_off[e + 1] - sh.core_off[e], p = sorted_lower_bound(ids, n, x);
+    const bool in = p < n && ids[p] == x;
+    if (!union_mode) { if (!in) return false; continue; }
+    if (ecs.e[j] & EC_MATE1) { has1 = true; in1 = in1 || in; }
+    if (ecs.e[j] & EC_MATE2) { has2 = true; in2 = in2 || in; }
+  }
+  return !union_mode ? ecs.n > 0 : ((in1 || !has1) && (in2 || !has2));
+}
+// smallest shade >= from among the shades of the item's sets whose colour is in the result; NO_TARGET when there is none
+KAMD_HD uint32_t next_shade(const ShadeTables& sh, const EcList& ecs, bool union_mode, uint32_t from) {
+  for (;;) {
+    uint32_t x = NO_TARGET;
+    for (int j = 0; j < ecs.n; j++) {
+      const uint32_t e = ecs.e[j] & EC_ID_MASK;
+      const uint32_t* ids = sh.shade_ids + sh.shade_off[e];
+      const uint64_t n = sh.shade_off[e + 1] - sh.shade_off[e], p = sorted_lower_bound(ids, n, from);
+      if (p < n && ids[p] < x) x = ids[p];
+    }
+    if (x == NO_TARGET || core_result_has(sh, ecs, union_mode, sh.colour[x])) return x;
+    from = x + 1;
+  }
+}
+// for_each_in_set on an index with shades: the cores' result with the surviving shades merged in, in increasing order
+template <class F>
+KAMD_HD void for_each_in_shaded_set(const ShadeTables& sh, const EcList& ecs, bool union_mode, uint32_t* cur, F&& f) {
+  if (ecs.n == 0) return;
+  const SetTables core{sh.core_off, sh.core_ids};
+  uint32_t pend = next_shade(sh, ecs, union_mode, 0);
+  for_each_in_set(core, ecs, union_mode, cur, [&](uint32_t x) {
+    while (pend < x) { f(pend); pend = next_shade(sh, ecs, union_mode, pend + 1); }
+    f(x);
+  });
+  while (pend != NO_TARGET) { f(pend); pend = next_shade(sh, ecs, union_mode, pend + 1); }
+}
+// set_size_bound with shades: the bound of the cores' result plus the shades of all sets
+KAMD_HD uint64_t shaded_size_bound(const ShadeTables& sh, const uint32_t* e, int n, bool union_mode) {
+  const SetTables core{sh.core_off, sh.core_ids};
+  uint64_t b = set_size_bound(core, e, n, union_mode);
+  for (int j = 0; j < n; j++) { const uint32_t x = e[j] & EC_ID_MASK; b += sh.shade_off[x + 1] - sh.shade_off[x]; }
+  return b;
+}
+
 // Outcome of intersectKmers' emptiness rules (MinCollector.cpp:172-202) given per-mate facts.
 // Returns true when the item is pseudoaligned to the intersection of the collected (non-empty) sets.
 KAMD_HD bool pair_is_mapped(const MateInfo& a, const MateInfo& b) {

@@ -79,7 +79,7 @@ namespace kamdi {
 void apply_quant_opts(kamd_ctx* c, const kamd_quant_opts* o) {
   c->ix.no_jump = o->no_jump ? 1 : 0;
   c->ix.union_mode = o->do_union ? 1 : 0;
-  c->ix.comprehensive = (o->strand != 0 && (o->no_jump || o->do_union)) ? 1 : 0;   // ProcessReads.cpp:1139-1140
+  c->ix.comprehensive = (o->strand != 0 && (o->no_jump || o->do_union || c->ix.n_shades)) ? 1 : 0;   // ProcessReads.cpp:1139-1140
 }
 void apply_tuning(kamd_ctx* c) {
   c->items_per_wave = c->tune.items_per_wave; c->refill_min = c->tune.refill_min;
@@ -234,12 +234,22 @@ extern "C" int kamd_index_upload(kamd_ctx* c, const kamd_index* hix) {
   for (u64 u = 0; u < v.n_uec; u++) ecn[u] = v.uec_ec[u] | (ne[v.uec_ec[u]] ? 0x80000000u : 0u);
   if (int rc = upload(c, ecn.data(), v.n_uec, &d.uec_ecn)) return rc;
   if (int rc = upload(c, v.onlist_bits, v.onlist_words, &d.onlist_bits)) return rc;
+  d.n_shades = v.n_shades;
+  if (v.n_shades) {   // (an index without shades allocates nothing here)
+    if (int rc = upload(c, (const u64*)v.core_off, v.n_ecs + 1, &d.core_off)) return rc;
+    if (int rc = upload(c, v.core_ids, (size_t)v.core_nnz, &d.core_ids)) return rc;
+    if (int rc = upload(c, (const u64*)v.shade_off, v.n_ecs + 1, &d.shade_off)) return rc;
+    if (int rc = upload(c, v.shade_ids, (size_t)v.shade_nnz, &d.shade_ids)) return rc;
+    if (int rc = upload(c, v.shade_colour, (size_t)v.n_targets, &d.shade_colour)) return rc;
+  }
   {
-    // bitmaps of the large transcript sets (kamd_dev.h DevIndex): the largest first while they fit BM_MAX_BYTES
+    // bitmaps of the large transcript sets (kamd_dev.h DevIndex): the largest first while they fit BM_MAX_BYTES.  On an index with shades they
+    // describe the CORES: only EC resolution tests them (k_resolve, k_resolve_big), and it intersects cores there
+    const uint64_t* boff = v.n_shades ? v.core_off : v.ec_off;
     const u64 n_ids = v.n_targets + v.dlist_size;
     const u32 stride = (u32)((n_ids + 31) / 32);
     std::vector<std::pair<u64, u32>> big;   // (size, set)
-    for (u64 e = 0; e < v.n_ecs; e++) { const u64 sz = v.ec_off[e + 1] - v.ec_off[e]; if (sz > BM_MIN_MEMBERS) big.emplace_back(sz, (u32)e); }
+    for (u64 e = 0; e < v.n_ecs; e++) { const u64 sz = boff[e + 1] - boff[e]; if (sz > BM_MIN_MEMBERS) big.emplace_back(sz, (u32)e); }
     std::sort(big.begin(), big.end(), [](const std::pair<u64, u32>& a, const std::pair<u64, u32>& b) { return a.first > b.first || (a.first == b.first && a.second < b.second); });
     const size_t fit = stride ? BM_MAX_BYTES / ((size_t)stride * 4) : 0;
     if (big.size() > fit) big.resize(fit);
@@ -260,7 +270,7 @@ extern "C" int kamd_index_upload(kamd_ctx* c, const kamd_index* hix) {
         HIPC(hipMemsetAsync(p, 0, big.size() * (size_t)stride * 4, c->stream));
         d_words = (const u32*)p;
       }
-      hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)big.size()), dim3(256), 0, c->stream, d.ec_off, d.ec_ids, d_which, stride, const_cast<u32*>(d_words));
+      hipLaunchKernelGGL(k_bm_fill, dim3((unsigned)big.size()), dim3(256), 0, c->stream, v.n_shades ? d.core_off : d.ec_off, v.n_shades ? d.core_ids : d.ec_ids, d_which, stride, const_cast<u32*>(d_words));
       HIPC(hipGetLastError());
       d.bm_words = d_words;
       HIPC(hipStreamSynchronize(c->stream));   // (stack-owned staging buffers)

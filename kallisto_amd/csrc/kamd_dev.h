@@ -65,14 +65,16 @@ struct DevIndex {
   const u32* utext;   // 2-bit text of all unitigs (kamd_core.h: text_canon)
   int no_jump;   // kamd_quant_opts::no_jump of the run (set by the entry points that take the options)
   int union_mode;     // kamd_quant_opts::do_union: per-mate unions instead of intersections (MinCollector.cpp:163-169)
-  int comprehensive;  // strand filter per hit (ProcessReads.cpp:62-82): a strand option together with --union / --no-jump
+  int comprehensive;  // strand filter per hit (ProcessReads.cpp:62-82): a strand option together with --union / --no-jump / an index with shades
+  // shades (kamd_core.h ShadeTables); n_shades == 0: an ordinary index, the pointers are null and nothing below is read
+  u64 n_shades; const u64* core_off; const u32* core_ids; const u64* shade_off; const u32* shade_ids; const u32* shade_colour;
 };
 // the k-mer table(s) as the per-item logic sees them; partial = match()'s `partial` argument = single-end reads
 __host__ __device__ inline kamd::Table make_table(const DevIndex& ix, bool partial) {
   kamd::Table t{(const uint64_t*)ix.table, ix.n_buckets};
   t.layout = (uint8_t)ix.table_layout; t.q = (uint8_t)ix.tag_q; t.dsh = (uint8_t)ix.tag_dsh; t.tagw = (uint8_t)ix.tag_w;
   t.dslots = (const uint64_t*)ix.dtable; t.n_dbuckets = ix.n_dbuckets; t.dummy_uec = ix.dummy_uec; t.dummy_slot = ix.dummy_slot;
-  t.dummy_strand = ix.dummy_strand != 0; t.partial = partial && !ix.union_mode;   // --union: match(..., partial = false) (KmerIndex.cpp:1704)
+  t.dummy_strand = ix.dummy_strand != 0; t.partial = partial && !ix.union_mode && !ix.n_shades;   // --union, shades: match(..., partial = false) (KmerIndex.cpp:1704)
   t.no_jump = ix.no_jump != 0;
   return t;
 }
@@ -91,6 +93,8 @@ struct DevState {
   u64 cand_words, cand_recs;     // candidate transcript-set stream
   u64 tl_n, ts_words, tl_fail;   // distinct tuples so far (entries of the tuple list), words of the tuple store, records of a batch that found no slot
   u64 n_big, n_huge;             // kamd_ec_finalize: distinct tuples whose smallest set has 17 .. 1024 / more than 1024 members (k_resolve_big's work lists)
+  u64 n_sh_small, n_sh_long;     // ... an index with shades: tuples whose sets hold shades, by the size of members + shades (k_shade_extend's work lists)
+  u64 shade_err;                 // k_shade_extend found a slot smaller than its own count of the shades needs (reported by kamd_ec_finalize)
 };
 
 // counters of kernel A (their own struct: chunks of kernel A run on one stream while another copies DevState to and fro)
@@ -146,10 +150,23 @@ __device__ __forceinline__ bool set_has(const DevIndex& ix, u32 e, u64 off, u32 
   if (sz > ix.bm_min) { const u32 s = ix.ec_bm_slot[e]; if (s != BM_NONE) return bitmap_has(ix, s, x); }
   return set_contains(ix.ec_ids + off, sz, x);
 }
+__host__ __device__ inline kamd::ShadeTables shade_tables(const DevIndex& ix) {
+  return kamd::ShadeTables{(const uint64_t*)ix.core_off, ix.core_ids, (const uint64_t*)ix.shade_off, ix.shade_ids, ix.shade_colour};
+}
+// The index as EC resolution intersects it when it has shades: the cores in the place of the sets (the bitmaps describe the cores already,
+// kamd_index_upload), no shade tables -- k_resolve / k_resolve_big run on it unchanged, k_shade_extend puts the shades back
+__host__ __device__ inline DevIndex core_view(DevIndex ix) {
+  if (ix.n_shades) { ix.ec_off = ix.core_off; ix.ec_ids = ix.core_ids; ix.n_shades = 0; }
+  return ix;
+}
 // f(tr) for every on-listed member of the item's transcript set (intersection of its sets, or the per-mate unions intersected
 // with --union), in increasing order; thread-serial.  cur: ecs.n words of scratch for the --union merge.
 template <class F>
 __device__ __forceinline__ void for_each_member(const DevIndex& ix, const kamd::EcList& ecs, u32* cur, F&& f) {
+  if (ix.n_shades) {   // (the class rule of an index with shades: kamd_core.h for_each_in_shaded_set)
+    kamd::for_each_in_shaded_set(shade_tables(ix), ecs, ix.union_mode != 0, cur, [&](u32 x) { if (onlisted(ix.onlist_bits, x)) f(x); });
+    return;
+  }
   const kamd::SetTables st{(const uint64_t*)ix.ec_off, ix.ec_ids};
   kamd::for_each_in_set(st, ecs, ix.union_mode != 0, cur, [&](u32 x) { if (onlisted(ix.onlist_bits, x)) f(x); });
 }
@@ -177,14 +194,20 @@ __device__ __forceinline__ kamd::FilterCfg item_filter_cfg(const FilterDev& fd, 
 __device__ __forceinline__ bool needs_hit_list(const FilterDev& fd, const kamd::MateInfo& m1) {
   return fd.comprehensive != 0 && fd.strand != 0 && m1.n_hits == 0;
 }
+// what a record of the item's class may need at most (kamd_core.h set_size_bound; with shades shaded_size_bound).  Not inlined: it sits in
+// kernels whose item loops are unrolled
+__device__ __noinline__ u32 class_size_bound(const DevIndex& ix, const kamd::EcList& ecs) {
+  if (ix.n_shades) return (u32)kamd::shaded_size_bound(shade_tables(ix), ecs.e, ecs.n, ix.union_mode != 0);
+  const kamd::SetTables st{(const uint64_t*)ix.ec_off, ix.ec_ids};
+  return (u32)kamd::set_size_bound(st, ecs.e, ecs.n, ix.union_mode != 0);
+}
 // 0 = the filters leave the set unchanged, 1 = they empty it, 2 = they change it (*kept = new size)
 __device__ __forceinline__ int filter_outcome(const DevIndex& ix, const FilterDev& fd, bool paired, const kamd::MateInfo& m0,
                                               const kamd::MateInfo& m1, const kamd::EcList& ecs, u32* kept, u32* cur) {
   const kamd::FilterCfg cfg = item_filter_cfg(fd, paired, m0, m1);
   if (!cfg.fraglen && !cfg.strand) return 0;
   if (needs_hit_list(fd, m1)) {   // decided by the explicit-set pass; the record is at most the unfiltered set
-    const kamd::SetTables st{(const uint64_t*)ix.ec_off, ix.ec_ids};
-    *kept = (u32)kamd::set_size_bound(st, ecs.e, ecs.n, ix.union_mode != 0);
+    *kept = class_size_bound(ix, ecs);
     return 2;
   }
   const kamd::PosTables pt = pos_tables(ix);

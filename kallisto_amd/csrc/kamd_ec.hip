@@ -304,20 +304,37 @@ __global__ void k_tup_rehash(const u32* __restrict__ store, const TSlot* __restr
 // resolve: candidates = transcript sets of (a) index sets with a non-zero dense count, (b) distinct tuples
 // ------------------------------------------------------------------------------------------------------------------
 // upper bound of the candidate stream size: sum over candidates of (smallest list + 2)
+constexpr u64 SHADE_SMALL = 64;         // members + shades (bounds) up to which a 16-lane group extends a record; a wavefront beyond
+constexpr u64 SHADE_SLOT_FACTOR = 4;   // a tuple's slot on an index with shades: the merged record (cores' bound + S) + three arrays of S (k_shade_extend)
 constexpr u32 RES_BIG_MIN = 16;   // (= RES_LANES) a tuple whose smallest set has more members goes to k_resolve_big
 __global__ void k_bound_tuples(DevIndex ix, const u32* __restrict__ stream, const TSlot* table, const u64* list, u64 n,
-                               u32* per_tuple, u32* big_idx, DevState* st) {
+                               u32* per_tuple, u32* big_idx, u32* shade_idx, DevState* st) {
   u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   u64 b = 0;
-  bool big = false, huge = false;
+  bool big = false, huge = false, sh_small = false, sh_long = false;
   if (i < n) {
     const u64 off = list[i] >> 32;   // (the record's place in the store rides in the list entry: k_tup_store)
     const u32 m = stream[off + 1];
-    const kamd::SetTables stt{(const uint64_t*)ix.ec_off, ix.ec_ids};
-    b = kamd::set_size_bound(stt, stream + off + 2, (int)m, ix.union_mode != 0) + 2;   // smallest set / sum of the sets (--union)
+    u64 core_b;   // what the intersection kernels see: smallest set / sum of the sets (--union); on an index with shades, of the cores
+    if (ix.n_shades) {
+      // the slot also holds the shades: with --union the class itself (k_resolve_union writes it by the shaded rule); otherwise the cores'
+      // intersection, then k_shade_extend's three work arrays of S = all shades of the tuple's sets at its end, clear of the merged record
+      const kamd::ShadeTables sh = shade_tables(ix);
+      const kamd::SetTables core{sh.core_off, sh.core_ids};
+      core_b = kamd::set_size_bound(core, stream + off + 2, (int)m, ix.union_mode != 0);
+      const u64 S = kamd::shaded_size_bound(sh, stream + off + 2, (int)m, ix.union_mode != 0) - core_b;
+      b = core_b + (ix.union_mode ? S : SHADE_SLOT_FACTOR * S) + 2;
+      // the tuples k_shade_extend has work for: a 16-lane group where members + shades fit SHADE_SMALL words, a wavefront beyond
+      sh_small = !ix.union_mode && S != 0 && core_b + S <= SHADE_SMALL;
+      sh_long = !ix.union_mode && S != 0 && !sh_small;
+    } else {
+      const kamd::SetTables stt{(const uint64_t*)ix.ec_off, ix.ec_ids};
+      core_b = kamd::set_size_bound(stt, stream + off + 2, (int)m, ix.union_mode != 0);
+      b = core_b + 2;
+    }
     per_tuple[i] = (u32)b;   // the tuple's slot in the candidate stream (k_resolve writes there: no allocation at run time)
-    big = big_idx && !ix.union_mode && b - 2 > RES_BIG_MIN;
-    huge = big && b - 2 > 1024;   // (= RB_CAND_BIG)
+    big = big_idx && !ix.union_mode && core_b > RES_BIG_MIN;
+    huge = big && core_b > 1024;   // (= RB_CAND_BIG)
   }
   b = wave_sum64(b);
   if (lane_id() == 0 && b) atomicAdd(&st->bound_words, b);
@@ -334,6 +351,20 @@ __global__ void k_bound_tuples(DevIndex ix, const u32* __restrict__ stream, cons
     if (lane_id() == 0) base = atomicAdd(&st->n_huge, (u64)__popcll(hm));
     base = shfl_u64(base, 0);
     if (huge) big_idx[n - 1 - (base + __popcll(hm & ((1ULL << lane_id()) - 1ULL)))] = (u32)i;
+  }
+  // ... and of k_shade_extend, the same way (an index without shades: both masks are empty)
+  const u64 sm = __ballot(sh_small), lm = __ballot(sh_long);
+  if (sm) {
+    u64 base = 0;
+    if (lane_id() == 0) base = atomicAdd(&st->n_sh_small, (u64)__popcll(sm));
+    base = shfl_u64(base, 0);
+    if (sh_small) shade_idx[base + __popcll(sm & ((1ULL << lane_id()) - 1ULL))] = (u32)i;
+  }
+  if (lm) {
+    u64 base = 0;
+    if (lane_id() == 0) base = atomicAdd(&st->n_sh_long, (u64)__popcll(lm));
+    base = shfl_u64(base, 0);
+    if (sh_long) shade_idx[n - 1 - (base + __popcll(lm & ((1ULL << lane_id()) - 1ULL)))] = (u32)i;
   }
 }
 __global__ void k_bound_singles(DevIndex ix, const u32* __restrict__ dense, DevState* st) {
@@ -787,6 +818,103 @@ __global__ void k_resolve_union(DevIndex ix, const u32* __restrict__ stream, con
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// The shade extension of a candidate record (an index with shades, no --union): k_resolve / k_resolve_big have written r = the intersection of
+// the tuple's CORES into the tuple's slot; the class is r plus every shade of any of the tuple's sets whose colour is in r
+// (MinCollector.cpp:203-215), in increasing target id.  A group of W lanes per tuple -- W = 16, four tuples per wavefront, where members +
+// shades fit SHADE_SMALL words, W = 64 for the long ones: the split of k_cand_singles / k_resolve; k_bound_tuples made the two work lists, a
+// tuple whose sets hold no shade is in neither -- and everything inside the tuple's own slot: the slot was sized (k_bound_tuples) for the
+// merged record -- at most the cores' bound + S, S = the shades of all its sets, duplicates counted -- and, behind it and clear of it, three
+// arrays of S words: A the gathered shades, B "kept" flags (on-listed, colour in r by binary search, first occurrence), C the place of a
+// kept shade in the merged record = kept shades below it + members of r below it.  Then r's members move up by the number of kept shades
+// below them, from the back in runs of W (a run is read into registers before any of it is written; a member only moves up, to a place no
+// unread run holds), and the kept shades are dropped into the gaps.  No allocation, no atomics, no host round trip.  (The lanes of a group
+// take the same branches, so they stay in step; the fences order a phase's stores before the next phase's loads.)
+// ------------------------------------------------------------------------------------------------------------------
+constexpr u32 SHADE_NONE = 0xFFFFFFFFu;
+template <int W>
+__global__ __launch_bounds__(BLOCK) void k_shade_extend(DevIndex ix, const u32* __restrict__ stream, const u64* __restrict__ list,
+                                                        const u32* __restrict__ work, u64 n_work, const u64* __restrict__ slot_off,
+                                                        const u32* __restrict__ slot_cap, u32* cand, const u64* cand_off, DevState* st) {
+  const u64 wi = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / W;   // (group-uniform)
+  if (wi >= n_work) return;
+  const u64 gid = work[wi];
+  const u64 base_words = st->cand_words, base_recs = st->cand_recs;
+  if (cand_off[base_recs + gid] == ~0ULL) return;   // empty intersection: no class, no shades
+  const u32 sub = (u32)lane_id() & (u32)(W - 1);
+  const u64 owner = list[gid] >> 32;
+  const u32 m = stream[owner + 1];
+  const u32* es = stream + owner + 2;
+  u32 S = 0;
+  for (u32 j = sub; j < m; j += W) { const u32 e = es[j] & kamd::EC_ID_MASK; S += (u32)(ix.shade_off[e + 1] - ix.shade_off[e]); }
+#pragma unroll
+  for (int d = 1; d < W; d <<= 1) S += (u32)__shfl_xor((int)S, d, W);
+  if (S == 0) return;
+  u32* w = cand + base_words + slot_off[gid];
+  const u32 cap = slot_cap[gid];
+  const u32 nr = w[1];
+  u32* r = w + 2;
+  if ((u64)cap < 2ULL + nr + SHADE_SLOT_FACTOR * (u64)S) {   // k_bound_tuples sized the slot with the same S: a disagreement is a bug, and is reported
+    if (sub == 0) atomicOr((unsigned long long*)&st->shade_err, 1ULL);
+    return;
+  }
+  u32* A = w + cap - 3 * S; u32* B = A + S; u32* Cp = B + S;
+  // gather the sets' shade lists
+  u32 pos = 0;
+  for (u32 j = 0; j < m; j++) {
+    const u32 e = es[j] & kamd::EC_ID_MASK;
+    const u64 o = ix.shade_off[e]; const u32 cnt = (u32)(ix.shade_off[e + 1] - o);
+    for (u32 t = sub; t < cnt; t += W) A[pos + t] = ix.shade_ids[o + t];
+    pos += cnt;
+  }
+  __threadfence();
+  // kept: on-listed, colour in r, and the first of its value
+  for (u32 j = sub; j < S; j += W) {
+    const u32 x = A[j];
+    bool ok = onlisted(ix.onlist_bits, x) && set_contains(r, nr, ix.shade_colour[x]);
+    for (u32 k = 0; ok && k < j; k++) ok = A[k] != x;
+    B[j] = ok ? 1u : 0u;
+  }
+  __threadfence();
+  u32 ns = 0;
+  for (u32 j = sub; j < S; j += W) {
+    u32 at = SHADE_NONE;
+    if (B[j]) {
+      const u32 x = A[j];
+      u32 below = 0;
+      for (u32 k = 0; k < S; k++) below += (B[k] && A[k] < x) ? 1u : 0u;
+      u32 lo = 0, hi = nr;
+      while (lo < hi) { const u32 mid = (lo + hi) >> 1; if (r[mid] < x) lo = mid + 1; else hi = mid; }
+      at = below + lo;
+      ++ns;
+    }
+    Cp[j] = at;
+  }
+#pragma unroll
+  for (int d = 1; d < W; d <<= 1) ns += (u32)__shfl_xor((int)ns, d, W);
+  if (ns == 0) return;   // every shade failed the colour test
+  __threadfence();
+  // r's members move up, from the back
+  for (u32 hi = nr; hi > 0;) {
+    const u32 lo = hi > (u32)W ? hi - (u32)W : 0;
+    const u32 i = lo + sub;
+    const bool act = i < hi;
+    u32 x = 0, to = 0;
+    if (act) {
+      x = r[i];
+      u32 below = 0;
+      for (u32 k = 0; k < S; k++) below += (B[k] && A[k] < x) ? 1u : 0u;
+      to = i + below;
+    }
+    __threadfence();
+    if (act && to != i) r[to] = x;
+    __threadfence();
+    hi = lo;
+  }
+  for (u32 j = sub; j < S; j += W) if (Cp[j] != SHADE_NONE) r[Cp[j]] = A[j];
+  if (sub == 0) w[1] = nr + ns;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // exclusive scan of u32 sizes into u64 offsets (three kernels; sizes up to 2^31 elements)
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int SCAN_ELEMS = 2048;  // per block: 256 threads x 8
@@ -1132,14 +1260,15 @@ extern "C" int kamd_ec_finalize(kamd_ctx* c, kamd_ec_result* out) {
   const u64 n_t = c->n_distinct_tuples;   // (the batches' tuple records were absorbed as they came: absorb_tuples)
   // size bound of the candidate stream
   c->host_state.bound_words = 0; c->host_state.cand_words = 0; c->host_state.cand_recs = 0; c->host_state.n_big = 0; c->host_state.n_huge = 0;
+  c->host_state.n_sh_small = 0; c->host_state.n_sh_long = 0; c->host_state.shade_err = 0;
   if (int rc = push_state(c)) return rc;
   hipLaunchKernelGGL(k_bound_singles, dim3(grid_for(c->n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, c->ix, c->dense.as<u32>(), dst);
   if (int rc = c->tup_bound.ensure((n_t + 1) * sizeof(u32), 0, c->stream)) return rc;
   if (int rc = c->tup_off.ensure((n_t + 2) * sizeof(u64), 0, c->stream)) return rc;
-  if (int rc = c->tup_big.ensure((n_t + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->tup_big.ensure(2 * (n_t + 1) * sizeof(u32), 0, c->stream)) return rc;   // (k_resolve_big's work lists, then k_shade_extend's)
   if (n_t) {
     hipLaunchKernelGGL(k_bound_tuples, dim3(grid_for(n_t, BLOCK)), dim3(BLOCK), 0, c->stream, c->ix, c->tstore.as<u32>(),
-                       c->ttable.as<TSlot>(), c->list.as<u64>(), n_t, c->tup_bound.as<u32>(), c->tup_big.as<u32>(), dst);
+                       c->ttable.as<TSlot>(), c->list.as<u64>(), n_t, c->tup_bound.as<u32>(), c->tup_big.as<u32>(), c->tup_big.as<u32>() + (n_t + 1), dst);
     if (int rc = exclusive_scan(c, c->tup_bound.as<u32>(), n_t, c->tup_off.as<u64>(), c->tup_off.as<u64>() + n_t)) return rc;
   }
   HIPC(hipGetLastError());
@@ -1163,23 +1292,33 @@ extern "C" int kamd_ec_finalize(kamd_ctx* c, kamd_ec_result* out) {
                        c->ttable.as<TSlot>(), c->list.as<u64>(), n_t, c->tup_off.as<u64>(), c->cand.as<u32>(), c->cand_off.as<u64>(),
                        cand_key, big ? c->overflow_scratch.as<u32>() : nullptr, dst);
   } else if (n_t) {
-    hipLaunchKernelGGL(k_resolve, dim3(grid_for(n_t * RES_LANES, RES_BLOCK)), dim3(RES_BLOCK), 0, c->stream, c->ix, c->tstore.as<u32>(),
+    const DevIndex rix = core_view(c->ix);   // (an index with shades: the cores are intersected, k_shade_extend follows)
+    hipLaunchKernelGGL(k_resolve, dim3(grid_for(n_t * RES_LANES, RES_BLOCK)), dim3(RES_BLOCK), 0, c->stream, rix, c->tstore.as<u32>(),
                        c->ttable.as<TSlot>(), c->list.as<u64>(), n_t, c->tup_off.as<u64>(), c->cand.as<u32>(), c->cand_off.as<u64>(),
                        cand_key, dst);
     // the tuples whose smallest set is large (k_bound_tuples listed them): one wavefront each, the intersection out of LDS
     const u64 n_big = c->host_state.n_big, n_huge = c->host_state.n_huge;
-    if (n_big) hipLaunchKernelGGL(k_resolve_big<(int)RB_CAND_BIG>, dim3(grid_for(n_big, RB_WAVES)), dim3(64 * RB_WAVES), 0, c->stream, c->ix, c->tstore.as<u32>(),
+    if (n_big) hipLaunchKernelGGL(k_resolve_big<(int)RB_CAND_BIG>, dim3(grid_for(n_big, RB_WAVES)), dim3(64 * RB_WAVES), 0, c->stream, rix, c->tstore.as<u32>(),
                                   c->ttable.as<TSlot>(), c->list.as<u64>(), c->tup_big.as<u32>(), n_big, c->tup_off.as<u64>(), c->cand.as<u32>(),
                                   c->cand_off.as<u64>(), cand_key, dst);
-    if (n_huge) hipLaunchKernelGGL(k_resolve_big<(int)RB_CAND_HUGE>, dim3(grid_for(n_huge, RB_WAVES)), dim3(64 * RB_WAVES), 0, c->stream, c->ix, c->tstore.as<u32>(),
+    if (n_huge) hipLaunchKernelGGL(k_resolve_big<(int)RB_CAND_HUGE>, dim3(grid_for(n_huge, RB_WAVES)), dim3(64 * RB_WAVES), 0, c->stream, rix, c->tstore.as<u32>(),
                                    c->ttable.as<TSlot>(), c->list.as<u64>(), c->tup_big.as<u32>() + (n_t - n_huge), n_huge, c->tup_off.as<u64>(), c->cand.as<u32>(),
                                    c->cand_off.as<u64>(), cand_key, dst);
     c->last_fin_big = n_big + n_huge;
+    if (c->ix.n_shades) {   // the shades back into the records of the tuples whose sets hold any: 16-lane groups for the short ones, wavefronts for the long
+      const u64 n_s = c->host_state.n_sh_small, n_l = c->host_state.n_sh_long;
+      const u32* sw = c->tup_big.as<u32>() + (n_t + 1);
+      if (n_s) hipLaunchKernelGGL(k_shade_extend<16>, dim3(grid_for(n_s * 16, BLOCK)), dim3(BLOCK), 0, c->stream, c->ix, c->tstore.as<u32>(), c->list.as<u64>(), sw, n_s,
+                                  c->tup_off.as<u64>(), c->tup_bound.as<u32>(), c->cand.as<u32>(), c->cand_off.as<u64>(), dst);
+      if (n_l) hipLaunchKernelGGL(k_shade_extend<64>, dim3(grid_for(n_l * 64, BLOCK)), dim3(BLOCK), 0, c->stream, c->ix, c->tstore.as<u32>(), c->list.as<u64>(), sw + (n_t - n_l), n_l,
+                                  c->tup_off.as<u64>(), c->tup_bound.as<u32>(), c->cand.as<u32>(), c->cand_off.as<u64>(), dst);
+    }
     if (getenv("KAMD_DEBUG_FIN")) fprintf(stderr, "[kamd] finalize: %llu distinct tuples, smallest set 17..1024: %llu, beyond: %llu\n", (unsigned long long)n_t,
                                           (unsigned long long)n_big, (unsigned long long)n_huge);
   }
   HIPC(hipGetLastError());
   if (int rc = sync_state(c)) return rc;
+  if (c->host_state.shade_err) return kamd::fail(-4, "kamd_ec_finalize: a candidate slot is smaller than its shades need (k_bound_tuples and k_shade_extend disagree)");
   // the tuples' slots and record numbers follow what k_cand_singles allocated
   c->host_state.cand_words += tup_words; c->host_state.cand_recs += n_t;
   if (int rc = push_state(c)) return rc;

@@ -193,6 +193,12 @@ struct kamd_index {
   // device for the layout and load factor kept here
   bool deferred = false;
   int req_layout = KAMD_TABLE_AUTO; double req_load = 0.0;
+  // shades (targets named <base>_shade_<variant>, KmerIndex.cpp:236-244, 1505-1518): made by build_shade_tables when a kallisto index is loaded,
+  // carried by a flattened file; all empty when the index has no shade
+  uint64_t n_shades = 0;
+  std::vector<uint32_t> shade_colour;                 // per target its base target (0xFFFFFFFF for a target that is no shade)
+  std::vector<uint64_t> core_off, shade_off;          // per transcript set: its members that are no shades / that are shades
+  std::vector<uint32_t> core_ids, shade_ids;
 };
 
 namespace {
@@ -224,12 +230,92 @@ inline void for_each_kmer_rc(const uint8_t* packed, uint64_t len, int k, F&& f) 
 
 }  // namespace
 
+// ---- shades -----------------------------------------------------------------------------------------------------------------------
+// Target i is a shade iff its name holds "_shade_" behind a non-empty prefix; its colour is the first target whose name equals that prefix
+// among the targets before it (KmerIndex.cpp:1505-1518).  The reference falls into unordered_map::operator[] for a shade without such a
+// target and silently takes colour 0; that index is refused here.  Every transcript set is split into its core (no shades) and its shades:
+// the full sets stay as they are -- the positional tables are parallel to them.
+namespace {
+// The reference's builder adds the colour to every set that gets a shade (KmerIndex.cpp:372-380, 1063-1077).  The class rule here leans on it: a set
+// with an empty core is an empty set, a single set's class is the set itself.  An index that breaks it would get classes the reference does not give.
+bool shade_sets_hold_colours(const kamd_index& x) {
+  for (size_t e = 0; e + 1 < x.core_off.size(); e++) {
+    const uint32_t* core = x.core_ids.data() + x.core_off[e];
+    const uint64_t nc = x.core_off[e + 1] - x.core_off[e];
+    for (uint64_t j = x.shade_off[e]; j < x.shade_off[e + 1]; j++)
+      if (!std::binary_search(core, core + nc, x.shade_colour[x.shade_ids[j]])) return false;
+  }
+  return true;
+}
+int build_shade_tables(kamd_index& x) {
+  static const char TAG[] = "_shade_";
+  x.n_shades = 0;
+  x.shade_colour.clear(); x.core_off.clear(); x.shade_off.clear(); x.core_ids.clear(); x.shade_ids.clear();
+  const uint64_t nt = x.n_targets;
+  std::vector<uint32_t> colour;
+  std::unordered_map<std::string, uint32_t> first_of;   // name -> first target of that name
+  for (uint64_t i = 0; i < nt && i < x.target_names.size(); i++) {
+    const std::string& nm = x.target_names[i];
+    const size_t at = nm.find(TAG);
+    if (at != std::string::npos && at != 0) {
+      const auto it = first_of.find(nm.substr(0, at));
+      if (it == first_of.end())
+        return kamd::fail(-3, "index: shade target '" + nm + "' has no base target '" + nm.substr(0, at) + "' before it");
+      if (colour.empty()) colour.assign((size_t)nt, 0xFFFFFFFFu);
+      colour[i] = it->second;
+      ++x.n_shades;
+    }
+    first_of.emplace(nm, (uint32_t)i);
+  }
+  if (!x.n_shades) return 0;
+  x.shade_colour.swap(colour);
+  const size_t n_ecs = x.ec_off.size() - 1;
+  x.core_off.assign(n_ecs + 1, 0); x.shade_off.assign(n_ecs + 1, 0);
+  x.core_ids.reserve(x.ec_ids.size());
+  for (size_t e = 0; e < n_ecs; e++) {
+    for (uint64_t j = x.ec_off[e]; j < x.ec_off[e + 1]; j++) {
+      const uint32_t t = x.ec_ids[j];
+      if (t < nt && x.shade_colour[t] != 0xFFFFFFFFu) x.shade_ids.push_back(t); else x.core_ids.push_back(t);
+    }
+    x.core_off[e + 1] = x.core_ids.size(); x.shade_off[e + 1] = x.shade_ids.size();
+  }
+  if (!shade_sets_hold_colours(x)) return kamd::fail(-3, "index: a transcript set holds a shade without its base target (not an index the reference's builder writes)");
+  return 0;
+}
+// the tables a flattened file brought: every length, every value the kernels use as an index, and the split itself (a set's core and shades are
+// its members that are no shades / that are shades, in order)
+bool shade_tables_consistent(const kamd_index& x) {
+  if (!x.n_shades) return x.shade_colour.empty() && x.core_off.empty() && x.core_ids.empty() && x.shade_off.empty() && x.shade_ids.empty();
+  const size_t n_ecs = x.ec_off.size() - 1;
+  if (x.shade_colour.size() != x.n_targets || x.core_off.size() != n_ecs + 1 || x.shade_off.size() != n_ecs + 1 || x.core_off[0] != 0 || x.shade_off[0] != 0 ||
+      x.core_off.back() != x.core_ids.size() || x.shade_off.back() != x.shade_ids.size() || x.core_ids.size() + x.shade_ids.size() != x.ec_ids.size()) return false;
+  uint64_t n = 0;
+  for (uint64_t t = 0; t < x.n_targets; t++) {
+    const uint32_t c = x.shade_colour[t];
+    if (c == 0xFFFFFFFFu) continue;
+    if (c >= t || x.shade_colour[c] != 0xFFFFFFFFu) return false;   // (a colour comes before its shade and is no shade itself)
+    ++n;
+  }
+  if (n != x.n_shades) return false;
+  for (size_t e = 0; e < n_ecs; e++) {
+    uint64_t a = x.core_off[e], b = x.shade_off[e];
+    if (x.core_off[e + 1] < a || x.shade_off[e + 1] < b || (x.core_off[e + 1] - a) + (x.shade_off[e + 1] - b) != x.ec_off[e + 1] - x.ec_off[e]) return false;
+    for (uint64_t j = x.ec_off[e]; j < x.ec_off[e + 1]; j++) {
+      const uint32_t t = x.ec_ids[j];
+      const bool sh = t < x.n_targets && x.shade_colour[t] != 0xFFFFFFFFu;
+      if (sh ? x.shade_ids[b++] != t : x.core_ids[a++] != t) return false;
+    }
+  }
+  return shade_sets_hold_colours(x);
+}
+}  // namespace
+
 // ---- the flattened index as a file (kamd_index_save / kamd_index_load on such a file) ------------------------------------------
 // Building the device tables from a kallisto index takes seconds (enumerate the k-mers of every unitig twice, hash, place); a
 // front-end that runs sample after sample against one index can write them once and read them back with plain reads.  Layout:
 // magic, format version, the scalars, then every array as {u64 count, bytes}; native endianness, for this machine's eyes only.
 namespace {
-const char FLAT_MAGIC[8] = {'K', 'A', 'M', 'D', 'F', 'L', 'T', '4'};   // 4: the source index's identity behind the stamp
+const char FLAT_MAGIC[8] = {'K', 'A', 'M', 'D', 'F', 'L', 'T', '5'};   // 5: the shade tables behind the other arrays (4: the source index's identity behind the stamp)
 // what the layout of the tables depends on, written behind the magic and compared on load
 const uint32_t FLAT_STAMP[4] = {(uint32_t)kamd::BUCKET_SLOTS, (uint32_t)sizeof(uint64_t) * 8u /* bytes per bucket */, 30u /* bits of a class id in the payload */, 13u /* kallisto index version */};
 // identity of a kallisto index file: FNV-1a over its size and its first and last 64 KiB (header, k, start of the graph; transcript names and
@@ -320,6 +406,7 @@ template <class IO> void flat_fields(IO& io, kamd_index& x) {
   io.vec(x.unitig_len); io.vec(x.unitig_blk_off); io.vec(x.blk_unitig); io.vec(x.blk_lb); io.vec(x.blk_ub); io.vec(x.blk_ec); io.vec(x.blk_uec);
   io.vec(x.blk_pos_off); io.vec(x.blk_posw); io.vec(x.blk_sense); io.vec(x.uec_ec); io.vec(x.ec_off); io.vec(x.ec_ids); io.vec(x.target_lens);
   io.vec(x.onlist_bits); io.vec(x.table); io.vec(x.slot_block); io.vec(x.slot_dist); io.vec(x.utext); io.vec(x.unitig_gpos); io.vec(x.dlist_keys); io.vec(x.dtable);
+  io.scalar(x.n_shades); io.vec(x.shade_colour); io.vec(x.core_off); io.vec(x.core_ids); io.vec(x.shade_off); io.vec(x.shade_ids);
 }
 using kamd::ixb::compact_shifts;   // (the geometry of the table: kamd_ixbuild.h, shared with the device builder)
 bool layout_is_consistent(const kamd_index& x) {
@@ -385,6 +472,7 @@ int load_flat(const char* path, int threads, kamd_index** out) {
       good = ok2;
     }
   }
+  if (good) good = shade_tables_consistent(*ix);
   if (!good) return kamd::fail(-3, std::string("flattened index file is damaged or of another format version: ") + path);
   *out = ix.release();
   return 0;
@@ -913,6 +1001,7 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     run_parallel([] { return 0; }, [&](uint64_t u, int&) { write_text(u); }, [](int&) {});
     tick("unitig text");
     ix->deferred = true; ix->req_layout = want_compact; ix->req_load = compact_load_arg;
+    if (int rc = build_shade_tables(*ix)) return rc;
     *out = ix.release();
     return 0;
   }
@@ -1065,6 +1154,7 @@ int load_index_impl(const char* path, int threads, int want_compact, double comp
     ix->dummy_slot = pd.slot; ix->dummy_uec = pd.uec; ix->dummy_strand = pd.strand ? 1 : 0;
   }
   tick("D-list table + dummy hit");
+  if (int rc = build_shade_tables(*ix)) return rc;
   *out = ix.release();
   return 0;
 }
@@ -1090,6 +1180,19 @@ extern "C" int kamd_index_get_view(const kamd_index* ix, kamd_index_view* v) {
   v->dummy_slot = ix->dummy_slot; v->dummy_uec = ix->dummy_uec; v->dummy_strand = ix->dummy_strand;
   v->utext = ix->utext.data(); v->utext_words = ix->utext.size(); v->text_bases = ix->text_bases;
   v->unitig_gpos = ix->unitig_gpos.data();
+  v->n_shades = ix->n_shades;
+  if (ix->n_shades) {
+    v->shade_colour = ix->shade_colour.data();
+    v->core_off = ix->core_off.data(); v->core_ids = ix->core_ids.data(); v->core_nnz = ix->core_ids.size();
+    v->shade_off = ix->shade_off.data(); v->shade_ids = ix->shade_ids.data(); v->shade_nnz = ix->shade_ids.size();
+  }
+  return 0;
+}
+
+extern "C" int kamd_index_check_opts(const kamd_index* ix, const kamd_quant_opts* o) {
+  if (!ix || !o) return kamd::fail(-1, "kamd_index_check_opts: null argument");
+  if (ix->n_shades && o->fld != 0.0 && !o->single_overhang)
+    return kamd::fail(-5, "an index with shades cannot take the positional fragment-length filter (-l / -s without --single-overhang)");
   return 0;
 }
 

@@ -1066,6 +1066,10 @@ extern "C" int kamd_pseudoalign(kamd_ctx* c, const kamd_quant_opts* o, const uin
     // (the reference itself aborts there: findPosition looks the union's transcripts up in the first mapping k-mer's set,
     // "Index not present in SparseVector")
     return kamd::fail(-5, "kamd_pseudoalign: --single with --union needs --single-overhang");
+  if (c->ix.n_shades && o->fld != 0.0 && !o->single_overhang)
+    // (the same abort of the reference: the positional fragment-length filter asks findPosition about a shade that is not in the first
+    // mapping k-mer's set -- --single without --single-overhang, and paired reads with -l / -s, whose orphan mates reach the filter)
+    return kamd::fail(-5, "kamd_pseudoalign: an index with shades cannot take the positional fragment-length filter (-l / -s without --single-overhang)");
   apply_quant_opts(c, o);
   if (max_len <= 0 || max_len > 65535) return kamd::fail(-1, "kamd_pseudoalign: max_len must be in [1, 65535]");
   if (n_items == 0) return 0;

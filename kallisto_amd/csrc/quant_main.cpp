@@ -305,8 +305,9 @@ int main(int argc, char** argv) {
     if (ix_state < 0 && err) *err = ix_err;
     return ix_state > 0;
   };
+  std::atomic<bool> ix_err_in_feed{false};   // a batch failed on the index error: the feed reports that very message
   auto run_batch = [&](int g, PackedBatch& b, std::string& err) -> int {
-    if (!index_ready(&err)) return -1;
+    if (!index_ready(&err)) { ix_err_in_feed = true; return -1; }
     const bool want_fld = g == 0 && paired && opt.fld == 0.0 && fld_used < 10000;
     int rc = 0;
     if (want_fld) rc = kamd_fld_prefetch(ctxs[g], &qo, b.d_words, b.d_len, b.n_items, b.max_len);   // runs underneath kernel A
@@ -324,6 +325,11 @@ int main(int argc, char** argv) {
     load_early.join();
     if (load_rc) { done(-1, load_err); return; }
     std::cerr << "\n[index] k-mer length: " << v.k << "\n[index] number of targets: " << v.n_targets << "\n[index] number of k-mers: " << v.n_kmers << std::endl;
+    if (v.n_shades) {   // (KmerIndex.cpp:1539-1542)
+      std::cerr << "[build] number of shades: " << v.n_shades << std::endl;
+      // (the reference aborts there: its positional fragment-length filter looks a shade up in a set that does not hold it)
+      if (kamd_index_check_opts(idx, &qo)) { done(-1, kamd_last_error()); return; }
+    }
     std::vector<std::thread> th; std::vector<int> rcs((size_t)n_gpus, 0); std::vector<std::string> errs((size_t)n_gpus);
     for (int g = 0; g < n_gpus; g++) th.emplace_back([&, g] {   // the index is replicated in every GPU's HBM
       rcs[g] = kamd_index_upload(ctxs[g], idx);
@@ -364,7 +370,8 @@ int main(int argc, char** argv) {
     if (paired) std::cerr << "                             " << opt.files[fi + 1] << std::endl;
   }
   const int feed_rc = feed_files(opt.files, paired, opt.batch, std::max(1, opt.threads), opt.threads, opt.verbose, pipe, n_processed, pack_s, &feeder, reset_run);
-  { std::string e; if (!index_ready(&e)) { std::cerr << "Error: " << e << std::endl; return 1; } }   // (also when there was no read to wait for it)
+  // (also when there was no read to wait for it; not a second time when the feed failed on this very error and has printed it)
+  { std::string e; if (!index_ready(&e)) { if (!(feed_rc && ix_err_in_feed)) std::cerr << "Error: " << e << std::endl; return 1; } }
   if (feed_rc) return 1;
   pipe.finish();
   if (pipe.failed()) { std::cerr << "Error: " << pipe.error() << std::endl; return 1; }

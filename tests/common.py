@@ -9,7 +9,9 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = ["ref_test_pe", "yeast_se", "human_pe", "tiny_k7_se", "dlist_pe", "mosaic_pe", "stress_pe"]
+CASES = ["ref_test_pe", "yeast_se", "human_pe", "tiny_k7_se", "dlist_pe", "mosaic_pe", "stress_pe",
+         # k between 7 and 31: the third read word of a window, the 32-bit key boundary (15 / 17), 2 .. 26 key bits in the compact table's tag
+         "k11_pe", "k15_pe", "k17_pe", "k21_pe", "k25_pe", "k29_pe"]
 MAX_FRAG_LEN = 1000
 
 

@@ -6,7 +6,7 @@
 Each case directory holds
     index.idx            built by `kallisto index` (reference binary)
     reads_1.txt.gz [reads_2.txt.gz]   one read per line
-    expected_<variant>.txt            output of oracle/_ref/dump_ec quant ... (NPROC / EC / FLEN / TR [/ BS] lines)
+    expected_<variant>.txt            output of oracle/_ref/dump_ec quant ... (NPROC / EC / FLEN / TR [/ BS] lines; .txt.gz in the k11_pe .. k29_pe cases)
     case.json                         how the case was made (seeds, options per variant)
 The fixtures are small on purpose (a few hundred kB each); they pin the oracle (tests/test_oracle_golden.py) and the
 HIP path (tests/test_gpu_parity.py) without needing /root/reference at test time.
@@ -52,7 +52,9 @@ def write_fastq(path, reads):
             f.write(b"@r%d\n%s\n+\n%s\n" % (i, s, b"I" * len(s)))
 
 
-def make_case(name, fasta_path, reads1, reads2, variants, k=31, note="", index_args=()):
+def make_case(name, fasta_path, reads1, reads2, variants, k=31, note="", index_args=(), compact=False):
+    """compact: expected_<variant>.txt.gz instead of .txt (common.load_expected reads either) and no cli_<variant> directories -- for cases
+    that no front-end test runs"""
     if ONLY and name not in ONLY:
         return
     d = os.path.join(HERE, name)
@@ -75,6 +77,10 @@ def make_case(name, fasta_path, reads1, reads2, variants, k=31, note="", index_a
             vfiles = files[:1] if "--single" in extra else files   # single-end variants of a paired case use mate 1 only
             out = subprocess.run([DUMP, "quant", idx, "1", *extra, *vfiles], check=True, stdout=subprocess.PIPE,
                                  stderr=subprocess.DEVNULL).stdout
+            if compact:
+                with open(os.path.join(d, f"expected_{vname}.txt.gz"), "wb") as f, gzip.GzipFile(fileobj=f, mode="wb", compresslevel=9, mtime=0) as g:
+                    g.write(out)
+                continue
             with open(os.path.join(d, f"expected_{vname}.txt"), "wb") as f:
                 f.write(out)
             # the reference CLI itself (`kallisto quant -t 1 --plaintext`): abundance.tsv, bs_abundance_*.tsv, run_info.json
@@ -117,6 +123,123 @@ def read_fastq_gz(path):
             if i % 4 == 1:
                 out.append(line.rstrip(b"\r\n"))
     return out
+
+
+MID_K = (11, 15, 17, 21, 25, 29)
+# (seed of the transcriptome, seed of the reads) per k: changed only when a seed puts a transcript on the EM's zeroing threshold
+MID_K_SEEDS = {11: (111, 211), 15: (115, 215), 17: (117, 217), 21: (121, 221), 25: (125, 225), 29: (129, 229)}
+
+
+def _special_lengths(k):
+    """read lengths around everything that depends on k or on the 32-bit words of a packed read"""
+    return sorted({k - 2, k - 1, k, k + 1, 2 * k - 1, 2 * k, 2 * k + 1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 63, 64, 65, 150})
+
+
+def _ragged_pairs(seqs, k, rng, base_len):
+    """About 200 pairs for one intermediate-k case: every length of _special_lengths(k) as equal mates and against a mate of
+    base_len bases on either side, all-N reads, an N in the last base of the first k-mer (position k-1) and in the first base of
+    the last one (position len-k), lower-case reads.  Fragments come from transcripts that are long enough, half of them from the
+    reverse strand, with 0.5 % substitutions."""
+    lens = np.array([len(s) for s in seqs])
+
+    def pair(l1, l2):
+        need = max(l1, l2, 1)
+        t = int(rng.choice(np.flatnonzero(lens >= need)))
+        fl = int(min(lens[t], max(need, int(rng.normal(180, 20)))))
+        a = int(rng.integers(0, lens[t] - fl + 1))
+        frag = seqs[t][a:a + fl]
+        if rng.random() < 0.5:
+            frag = synth.revcomp(frag)
+        m = [frag[:l1].copy(), synth.revcomp(frag[fl - l2:]).copy() if l2 else frag[:0].copy()]
+        for r in m:
+            e = rng.random(len(r)) < 0.005
+            r[e] = synth._ACGT[rng.integers(0, 4, int(e.sum()))]
+        return bytes(m[0]), bytes(m[1])
+
+    def with_n(r, pos):
+        return r[:pos] + b"N" + r[pos + 1:] if 0 <= pos < len(r) else r
+    out = []
+    for L in _special_lengths(k):
+        out += [pair(L, L) for _ in range(5)] + [pair(L, base_len), pair(base_len, L), pair(L, L + 7), pair(150, L)]
+    for L in (base_len, 2 * k + 1, 150):
+        a, b = pair(L, L); out.append((b"N" * L, b))                        # one mate all N
+        a, b = pair(L, L); out.append((a, b"N" * L))
+        out.append((b"N" * L, b"N" * L))                                      # both
+        a, b = pair(L, L); out.append((with_n(a, k - 1), b))                 # N in the last base of the first k-mer
+        a, b = pair(L, L); out.append((a, with_n(b, L - k)))                 # N in the first base of the last k-mer
+        a, b = pair(L, L); out.append((with_n(with_n(a, k - 1), L - k), with_n(with_n(b, k - 1), L - k)))
+        a, b = pair(L, L); out.append((a.lower(), b))
+        a, b = pair(L, L); out.append((a.lower(), b.lower()))
+    return out
+
+
+def _mid_k_transcriptome(k, seed):
+    if k >= 15:
+        return synth.human_like(n_genes=20, seed=seed), f"synth.human_like(20 genes, seed={seed})"
+    # k = 11: a human-like transcriptome is one tangled graph there.  A few dozen transcripts of 100-400 bp (tiny_k7_se's size), each a
+    # subset of its gene's eight random exons of 30-90 bp, so that the classes are not all single transcripts
+    rng = np.random.default_rng(seed)
+    seqs = []
+    for _ in range(6):
+        exons = [synth._ACGT[rng.integers(0, 4, int(l))] for l in rng.integers(30, 91, 8)]
+        seen = set()
+        while len(seen) < 8:
+            keep = rng.random(8) < 0.65
+            tr = np.concatenate([exons[i] for i in np.flatnonzero(keep)]) if keep.sum() >= 2 else exons[0][:0]
+            if keep.tobytes() in seen or not 100 <= len(tr) <= 400:
+                continue
+            seen.add(keep.tobytes())
+            seqs.append(tr)
+    return seqs, f"48 transcripts of 100-400 bp (seed={seed}): 6 genes of eight random exons of 30-90 bp, eight exon subsets each"
+
+
+def _case_figures(name):
+    """what the issue of the intermediate-k cases asks of a fixture, from the reference's own output"""
+    from tests import common
+    pe = common.load_expected(name, "pe")
+    nj = common.load_expected(name, "pe_nojump")
+    aligned = sum(pe["ecs"].values())
+    multi = sum(1 for s in pe["ecs"] if len(s) > 1)
+    return aligned / pe["nproc"], multi, nj["ecs"] != pe["ecs"]
+
+
+def make_mid_k_cases(tmp):
+    """One paired case per k in MID_K (the code that depends on k has its boundaries strictly between the k = 7 and k = 31 of the other cases):
+    3000 simulated pairs with errors and N's, about 200 of them overwritten by _ragged_pairs."""
+    differs = {}
+    for k in MID_K:
+        name = f"k{k}_pe"
+        if ONLY and name not in ONLY:
+            continue
+        tseed, rseed = MID_K_SEEDS[k]
+        seqs, what = _mid_k_transcriptome(k, tseed)
+        fa = os.path.join(tmp, name + ".fa")
+        synth.write_fasta(fa, seqs)
+        base_len, fm, fs = (100, 200, 30) if k >= 15 else (50, 110, 12)
+        r1, r2 = synth.simulate_reads(seqs, 3000, base_len, paired=True, frag_mean=fm, frag_sd=fs, err=0.005, n_frac=0.01, seed=rseed)
+        r1 = [bytes(x) for x in r1]; r2 = [bytes(x) for x in r2]
+        rng = np.random.default_rng(rseed + 1000)
+        special = _ragged_pairs(seqs, k, rng, base_len)
+        for i, (a, b) in zip(np.sort(rng.choice(len(r1), len(special), replace=False)), special):
+            r1[i], r2[i] = a, b
+        se = ["--single", "-l", str(fm), "-s", str(fs)]
+        make_case(name, fa, r1, r2, {"pe": [], "pe_nojump": ["--no-jump"], "pe_rf": ["--rf"], "pe_union": ["--union"], "se": se,
+                                     "se_overhang": se + ["--single-overhang"]}, k=k, compact=True)
+        frac, multi, differs[k] = _case_figures(name)
+        assert frac >= 0.30, (name, frac)
+        assert multi >= 100, (name, multi)
+        assert os.path.getsize(os.path.join(HERE, name, "index.idx")) <= 420_000, name
+        note = (f"k={k}: {what}; simulate_reads(3000 PE-{base_len}, err 0.5 %, 1 % reads with an N, seed={rseed}), {len(special)} pairs overwritten with "
+                f"mates of {', '.join(str(x) for x in _special_lengths(k))} bases (equal and unequal mates), all-N reads, N at position k-1 and len-k, "
+                f"lower case.  Reference: {100 * frac:.1f} % of the pairs pseudoalign, {multi} distinct multi-transcript classes in expected_pe.txt.gz, "
+                f"pe_nojump {'differs from' if differs[k] else 'equals'} pe")
+        p = os.path.join(HERE, name, "case.json")
+        meta = json.load(open(p))
+        meta["note"] = note
+        json.dump(meta, open(p, "w"), indent=1)
+        print(name, f"aligned {frac:.3f} multi-classes {multi} nojump differs {differs[k]}")
+    if len(differs) == len(MID_K):
+        assert any(differs.values()), "--no-jump changes nothing on any intermediate-k case: say so in the notes"
 
 
 def main():
@@ -248,6 +371,8 @@ def main():
               {"pe": [], "pe_union": ["--union"], "pe_rf": ["--rf"], "se": se, "pe_nojump": ["--no-jump"], "pe_boot": ["--boot", "2", "--seed", "11"]},
               note="synth.human_stress(150 genes, seed=7: 2 repeat families in 30 % of the genes' terminal exons, 3 x 30 paralog genes, 5 % poly-A tails); "
                    "simulate_reads(6000 PE-100, seed=41, 12 % off-transcriptome pairs from a background with repeat copies, 3' quality tail up to 5 %)")
+    # 8. k = 11 .. 29: k11_pe, k15_pe, k17_pe, k21_pe, k25_pe, k29_pe
+    make_mid_k_cases(tmp)
     shutil.rmtree(tmp)
 
 

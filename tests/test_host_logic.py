@@ -325,7 +325,7 @@ def test_index_loader_refuses_damaged_files(case, tmp_path):
 
 
 @pytest.mark.parametrize("layout", ["wide", "compact"])
-@pytest.mark.parametrize("case", ["human_pe", "dlist_pe", "tiny_k7_se"])
+@pytest.mark.parametrize("case", ["human_pe", "dlist_pe", "tiny_k7_se", "k17_pe", "k29_pe"])
 def test_flattened_index_file_round_trip(case, layout, tmp_path, monkeypatch):
     """kamd_index_save / kamd_index_load on the saved file: every table of the view, the scalars and the target names come back
     bit-identical (the front-end's `flatten` sub-command and `-i index.kamd`)."""
@@ -414,7 +414,7 @@ def test_flattened_index_file_round_trip(case, layout, tmp_path, monkeypatch):
 
 
 @pytest.mark.parametrize("load", [0.3, 0.75, 0.9])
-@pytest.mark.parametrize("case", ["human_pe", "dlist_pe"])
+@pytest.mark.parametrize("case", ["human_pe", "dlist_pe", "k17_pe", "k29_pe"])
 def test_compact_table_at_other_loads(case, load):
     """KAMD_TABLE_LOAD: a sparse table, and dense ones where keys sit several buckets from home -- beyond what the displacement field
     can say (14 buckets, or 6 when the class ids leave it three bits) the builder takes a larger table and counts again.  Every k-mer is still found with its own payload."""
@@ -470,7 +470,7 @@ def test_table_layout_through_the_abi_and_the_front_end(tmp_path):
         assert subprocess.run([exe, "flatten", "-i", p, "-o", flat, "--kmer-table", "dense"], stderr=subprocess.DEVNULL).returncode != 0
 
 
-@pytest.mark.parametrize("case", ["human_pe", "dlist_pe", "mosaic_pe"])
+@pytest.mark.parametrize("case", ["human_pe", "dlist_pe", "mosaic_pe", "k17_pe", "k29_pe"])
 def test_dense_compact_table_through_the_kernels_stepper(case):
     """A compact table as dense as the builder lets it be (keys many buckets from home, long runs of continue flags): kernel A's
     one-line-per-step walk (stepper + unitig text, as k_match_v3 runs it) and the straight-line matcher give the sets of the wide table."""

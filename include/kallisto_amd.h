@@ -521,6 +521,35 @@ typedef struct {
 } kamd_aa_stats;
 int kamd_aa_stats_get(kamd_ctx*, kamd_aa_stats* out);
 
+/* ---- BGZF input inflated on the device ----
+ * A BGZF file is gzip cut into independent members of at most 64 KiB of text; a member's header says how long its raw DEFLATE stream is, its
+ * trailer the CRC-32 and the size of its text (ISIZE).  The caller walks the headers on the host, copies the *compressed* bytes to the device and
+ * describes every member; kamd_bgzf_inflate decodes the members (one wavefront each), checks every CRC-32 and counts the newlines.
+ * src_off / dst_off are arbitrary (no alignment); members may be given in any order and must not overlap in d_text; isize <= 65536,
+ * src_len <= 1 MiB.  d_comp itself must be 4-byte aligned and readable up to the next 4-byte boundary behind comp_bytes (the bit reader loads
+ * aligned dwords; any hipMalloc'ed buffer is): a misaligned d_comp is an argument error.
+ * A corrupt member never faults and never hangs: it is refused with a reason (kamd_inflate.h: 1 reads beyond src_len, 2 writes beyond ISIZE, 3 ends
+ * short of ISIZE, 4 distance before the member's text, 5 block type 3, 6 stored LEN != ~NLEN, 7 over-subscribed / incomplete code, 8 symbol outside
+ * the range, 9 malformed dynamic header, 10 CRC-32 mismatch) and its bytes are not written; bytes of d_text outside the members' destinations
+ * are never written.
+ * kamd_text_cut: the FASTQ front-end's cut of 1 or 2 device texts (d_text[f] 16-byte aligned and readable up to 32 bytes behind n_bytes[f], as for
+ * kamd_fastq_unit_parse) at whole records.  Runs on the context stream and synchronises it once. */
+typedef struct { uint64_t src_off; uint32_t src_len, isize, crc32, reserved; uint64_t dst_off; } kamd_bgzf_member;
+typedef struct { int32_t status;          /* 0 ok; 1 some member is corrupt: nothing of this call may be used */
+                 int32_t reason;          /* the decoder's reason code of the first bad member */
+                 uint64_t first_bad_member, n_bytes, n_newlines; } kamd_inflate_result;
+/* raw deflate streams at d_comp + src_off -> d_text + dst_off; members are independent; runs on the context stream, synchronises it once */
+int kamd_bgzf_inflate(kamd_ctx*, const uint8_t* d_comp, uint64_t comp_bytes, const kamd_bgzf_member* members /*host*/, uint64_t n_members,
+                      char* d_text, uint64_t text_cap, kamd_inflate_result* out);
+/* diagnostic (tools/inflate_rate.py): kamd_bgzf_inflate with the kernel's time by HIP events in *kernel_ms, and with check_crc = 0 the same
+   kernel without its CRC-32 / newline pass (the text is flushed unchecked, n_newlines = 0): the difference is what the check costs */
+int kamd_debug_bgzf_inflate(kamd_ctx*, const uint8_t* d_comp, uint64_t comp_bytes, const kamd_bgzf_member* members, uint64_t n_members,
+                            char* d_text, uint64_t text_cap, int32_t check_crc, kamd_inflate_result* out, float* kernel_ms);
+/* whole records at the head of 1 or 2 device texts: n_records = min over files of (lines / 4), capped by max_records;
+   end[f] = offset just behind line 4 * n_records of text f */
+int kamd_text_cut(kamd_ctx*, const char* const* d_text, const uint64_t* n_bytes, int32_t n_files, uint64_t max_records,
+                  uint64_t* n_records, uint64_t* end);
+
 /* ---- the quant flow in one call (ProcessReads -> fragment-length model -> EMAlgorithm::run, src/main.cpp:2654-2730) ----
  * For a caller whose reads already sit in HBM in the packed layout: the batches are pseudoaligned in order (fragment-length sample:
  * the first 10 000 qualifying pairs of the input, src/ProcessReads.cpp:981-1017), with a communicator every rank passes its own

@@ -86,6 +86,16 @@ class _AaStats(C.Structure):
                 ("n_winner", C.c_uint64 * 6), ("last_translate_ms", C.c_float), ("last_match_ms", C.c_float)]
 
 
+class BgzfMember(C.Structure):
+    """kamd_bgzf_member: one BGZF member of a kamd_bgzf_inflate call (raw deflate stream at src_off of the compressed bytes -> isize bytes at dst_off)."""
+    _fields_ = [("src_off", C.c_uint64), ("src_len", C.c_uint32), ("isize", C.c_uint32), ("crc32", C.c_uint32), ("reserved", C.c_uint32),
+                ("dst_off", C.c_uint64)]
+
+
+class _InflateResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("reason", C.c_int32), ("first_bad_member", C.c_uint64), ("n_bytes", C.c_uint64), ("n_newlines", C.c_uint64)]
+
+
 class _TableInfo(C.Structure):
     """kamd_table_info: geometry of the context's device k-mer table, and what its build took when kamd_index_upload built it."""
     _fields_ = [("n_buckets", C.c_uint64), ("pad_buckets", C.c_uint64), ("table_layout", C.c_uint32), ("slots_per_bucket", C.c_uint32),
@@ -189,6 +199,10 @@ _SYMBOLS = {
     "kamd_cfc_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p]),
     "kamd_pseudoalign_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]),
     "kamd_aa_stats_get": (C.c_int, [C.c_void_p, C.POINTER(_AaStats)]),
+    "kamd_bgzf_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(_InflateResult)]),
+    "kamd_debug_bgzf_inflate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(_InflateResult),
+                                          C.POINTER(C.c_float)]),
+    "kamd_text_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]),
     "kamd_quant_batches": (C.c_int, [C.c_void_p, C.POINTER(QuantOpts), C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(_QuantOut)]),
     "kamd_mean_frag_lens_trunc": (None, [C.c_void_p, C.c_void_p]),
     "kamd_trunc_gaussian_fld": (None, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p]),
@@ -526,6 +540,36 @@ class Context:
         return {"n_processed": int(s.n_processed), "n_rejected_offlist": int(s.n_rejected_offlist), "n_all_empty": int(s.n_all_empty),
                 "n_frame_clashes": int(s.n_frame_clashes), "n_winner": [int(x) for x in s.n_winner],
                 "translate_ms": float(s.last_translate_ms), "match_ms": float(s.last_match_ms)}
+
+    # ---- BGZF input inflated on the device ----
+    def bgzf_inflate(self, comp, members, text, comp_bytes=None, text_cap=None, debug_check_crc=None) -> dict:
+        """kamd_bgzf_inflate: `members` (a sequence of (src_off, src_len, isize, crc32, dst_off)) of the compressed bytes in the uint8 device
+        tensor `comp` -> the uint8 device tensor `text`.  Returns status, reason, first_bad_member, n_bytes, n_newlines.
+        debug_check_crc True / False: kamd_debug_bgzf_inflate instead (with / without the kernel's CRC pass); the result also has kernel_ms."""
+        arr = (BgzfMember * max(len(members), 1))()
+        for i, (so, sl, isz, crc, do) in enumerate(members):
+            arr[i] = BgzfMember(int(so), int(sl), int(isz), int(crc), 0, int(do))
+        res = _InflateResult()
+        if debug_check_crc is not None:
+            ms = C.c_float(0.0)
+            _check(load_library().kamd_debug_bgzf_inflate(self._h, comp.data_ptr(), int(comp.numel() if comp_bytes is None else comp_bytes), arr, len(members),
+                                                          text.data_ptr(), int(text.numel() if text_cap is None else text_cap), 1 if debug_check_crc else 0,
+                                                          C.byref(res), C.byref(ms)), "kamd_debug_bgzf_inflate")
+            return {"status": int(res.status), "reason": int(res.reason), "first_bad_member": int(res.first_bad_member), "n_bytes": int(res.n_bytes),
+                    "n_newlines": int(res.n_newlines), "kernel_ms": float(ms.value)}
+        _check(load_library().kamd_bgzf_inflate(self._h, comp.data_ptr(), int(comp.numel() if comp_bytes is None else comp_bytes), arr, len(members),
+                                                text.data_ptr(), int(text.numel() if text_cap is None else text_cap), C.byref(res)), "kamd_bgzf_inflate")
+        return {"status": int(res.status), "reason": int(res.reason), "first_bad_member": int(res.first_bad_member), "n_bytes": int(res.n_bytes),
+                "n_newlines": int(res.n_newlines)}
+
+    def text_cut(self, texts, n_bytes, max_records: int):
+        """kamd_text_cut: whole records at the head of 1 or 2 uint8 device tensors (16-byte aligned, 32 readable bytes behind n_bytes[f]).
+        Returns (n_records, [end per text])."""
+        ptrs = (C.c_void_p * 2)(*[t.data_ptr() for t in texts], *([None] * (2 - len(texts))))
+        nb = (C.c_uint64 * 2)(*[int(n) for n in n_bytes], *([0] * (2 - len(texts))))
+        nrec, end = C.c_uint64(0), (C.c_uint64 * 2)(0, 0)
+        _check(load_library().kamd_text_cut(self._h, ptrs, nb, len(texts), int(max_records), C.byref(nrec), end), "kamd_text_cut")
+        return int(nrec.value), [int(end[i]) for i in range(len(texts))]
 
     def fld_prefetch(self, opts: QuantOpts, words, lens, n_items: int, max_len: int):
         """Start the FLD kernel for the first prefix of a batch on a side stream (kamd_fld_prefetch); fld_from_batch on the same

@@ -18,6 +18,7 @@
 #include <unordered_map>
 
 #include "kamd_frontend.h"
+#include "kamd_inflate_feed.h"
 
 namespace kamd_fe {
 namespace {
@@ -54,6 +55,7 @@ void usage_bus() {
             << "                              translated in six reading frames (single-end only; not with --union / --no-jump)\n"
             << "-t, --threads=INT             Host threads (default: 1)\n"
             << "    --index-build=host|device As in quant: where the k-mer table is built (default: host)\n"
+            << "    --inflate=host|device     As in quant: where BGZF input is inflated (default: host)\n"
             << "    --bus-per-read            output.bus with one record per pseudoaligned read (count 1), as the reference writes it; by default\n"
             << "                              the records of a sample and class are collapsed into one with their number in `count` -- what\n"
             << "                              `bustools sort` makes of the reference's file.  Either way the records are sorted by barcode and\n"
@@ -76,13 +78,14 @@ int bus_main(int argc, char** argv) {
   if (argc == 2) { usage_bus(); return 0; }
   std::string index, output, technology, batch_file, val;
   std::vector<std::string> files;
-  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false, aa = false;
+  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false, aa = false, inflate_device = false;
   int strand = 0, threads = 1;
   uint64_t batch = 4u << 20;
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     if (take(a, "-i", "--index", i, argc, argv, val)) index = val;
     else if (take(a, "-o", "--output-dir", i, argc, argv, val)) output = val;
+    else if (take(a, nullptr, "--inflate", i, argc, argv, val)) { if (!parse_inflate_option(val, &inflate_device)) return 1; }
     else if (take(a, nullptr, "--index-build", i, argc, argv, val)) {
       if (val != "host" && val != "device") { std::cerr << "Error: --index-build expects host or device" << std::endl; return 1; }
       index_build_device = val == "device";
@@ -230,6 +233,7 @@ int bus_main(int argc, char** argv) {
     return rc;
   };
   UnitFeeder feeder({ctx}, {0}, run_batch, [] { return false; });
+  std::unique_ptr<InflateFeeder> inflater(inflate_device ? new InflateFeeder(ctx, 0, run_batch) : nullptr);
   for (size_t sidx = 0; sidx < batch_files.size(); sidx++) {
     KX(kamd_ec_reset(ctx));                         // a sample starts from an empty collector
     flens = sample_flens[sidx].data();
@@ -237,7 +241,7 @@ int bus_main(int argc, char** argv) {
     {
       MultiPipe pipe(1, run_batch, [] { return false; });
       auto reset_sample = [&]() -> int { std::fill(sample_flens[sidx].begin(), sample_flens[sidx].end(), 0u); fld_used = 0; return kamd_ec_reset(ctx); };
-      if (feed_files(batch_files[sidx], paired, batch, std::max(1, threads), threads, verbose, pipe, n_processed, pack_s, &feeder, reset_sample)) return 1;
+      if (feed_files_inflate(batch_files[sidx], paired, batch, std::max(1, threads), threads, verbose, pipe, n_processed, pack_s, &feeder, reset_sample, inflater.get(), true)) return 1;
       pipe.finish();
       if (pipe.failed()) { std::cerr << "Error: " << pipe.error() << std::endl; return 1; }
     }

@@ -7,6 +7,8 @@
 //   kamd_ctx.hip     context, index upload, tuning, diagnostics, communicators and what runs over them
 //   kamd_ixbuild.hip the k-mer table built on the device (upload of an index loaded with kamd_index_load_deferred), kamd_ctx_table_*
 //   kamd_aa.hip      translated search: the six comma-free frames of a read, match and frame rule (kamd_cfc_frames, kamd_pseudoalign_aa); per-item logic in kamd_aa.h
+//   kamd_inflate.hip BGZF members inflated on the device (k_bgzf_inflate, CRC-32), newline counts and the cut of whole records (kamd_bgzf_inflate, kamd_text_cut);
+//                    decoder in kamd_inflate.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -336,6 +338,8 @@ struct kamd_ctx {
   bool aa_ready = false;
   kamd_aa_stats aa_stats{};
   hipEvent_t aa_ev[3] = {nullptr, nullptr, nullptr};
+  // device-side inflate (kamd_inflate.hip): the call's member list and per-member {reason, newlines}; kamd_text_cut's per-chunk newline counts and its result
+  DBuf inf_members, inf_res, txt_counts, txt_res;
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 

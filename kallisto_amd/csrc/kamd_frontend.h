@@ -685,6 +685,13 @@ inline uint64_t onlist_targets(const kamd_index_view& v) {
   return n_on;
 }
 
+// --inflate host|device (quant, bus): where BGZF input is inflated.  false = the value is neither
+inline bool parse_inflate_option(const std::string& val, bool* device) {
+  if (val != "host" && val != "device") { std::cerr << "Error: --inflate expects host or device" << std::endl; return false; }
+  *device = val == "device";
+  return true;
+}
+
 int bus_main(int argc, char** argv);   // bus_main.cpp: `bus -x bulk`
 int tcc_main(int argc, char** argv);   // bus_main.cpp: `quant-tcc`
 

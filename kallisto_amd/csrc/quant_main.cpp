@@ -4,6 +4,7 @@
 // Host code only: FASTQ reading (FastqSequenceReader::fetchSequences, src/ProcessReads.cpp:3128-3267), batching,
 // writers.  Everything that computes runs on the GPU through libkallisto_amd.so.
 #include "kamd_frontend.h"
+#include "kamd_inflate_feed.h"
 
 namespace {
 using namespace kamd_fe;
@@ -13,6 +14,7 @@ struct Options {
   std::vector<std::string> files;
   bool single = false, single_overhang = false, plaintext = false, verbose = false, no_jump = false, do_union = false, share_device = false;
   int gpus = 1;
+  bool inflate_device = false;       // --inflate device: BGZF input is inflated by kamd_bgzf_inflate (kamd_inflate_feed.h); host: by the readers' threads
   bool index_build_device = false;   // --index-build device: the k-mer table is built by kamd_index_upload on the GPU (kamd_index_load_deferred)
   int table_layout = -1;   // --kmer-table: KAMD_TABLE_WIDE / _COMPACT / _AUTO; -1 = the library's choice (environment, default wide)
   int strand = 0, bootstrap = 0, threads = 1;
@@ -55,6 +57,8 @@ void usage() {
             << "                              four exact 16-byte slots (compact: 27 instead of 43 bytes per k-mer; auto = compact when it fits)\n"
             << "    --index-build=host|device the k-mer table is built while the index is loaded (host, default) or on the GPU when the index is\n"
             << "                              uploaded (device: the same table as a one-thread host build); a flattened .kamd file holds its table\n"
+            << "    --inflate=host|device     BGZF input (.fastq.gz written by bgzip) is inflated by host threads (host, default) or on the GPU (device:\n"
+            << "                              one GPU; other input is inflated on the host and a line says so)\n"
             << "    --share-device            with --gpus N: all N ranks on device 0, collectives staged through the host (runs the\n"
             << "                              several-GPU code path on a single-GPU box; for testing)\n";
 }
@@ -203,6 +207,7 @@ int main(int argc, char** argv) {
     else if (take(a, nullptr, "--kmer-table", i, argc, argv, val)) {
       if (!parse_table_layout(val, &opt.table_layout)) { std::cerr << "Error: --kmer-table expects wide, compact or auto" << std::endl; return 1; }
     }
+    else if (take(a, nullptr, "--inflate", i, argc, argv, val)) { if (!parse_inflate_option(val, &opt.inflate_device)) return 1; }
     else if (take(a, nullptr, "--index-build", i, argc, argv, val)) {
       if (val != "host" && val != "device") { std::cerr << "Error: --index-build expects host or device" << std::endl; return 1; }
       opt.index_build_device = val == "device";
@@ -369,7 +374,9 @@ int main(int argc, char** argv) {
     std::cerr << "[quant] will process " << (paired ? "pair " : "file ") << (fi / (paired ? 2 : 1) + 1) << ": " << opt.files[fi] << std::endl;
     if (paired) std::cerr << "                             " << opt.files[fi + 1] << std::endl;
   }
-  const int feed_rc = feed_files(opt.files, paired, opt.batch, std::max(1, opt.threads), opt.threads, opt.verbose, pipe, n_processed, pack_s, &feeder, reset_run);
+  std::unique_ptr<InflateFeeder> inflater(opt.inflate_device ? new InflateFeeder(ctx, devices[0], run_batch) : nullptr);
+  const int feed_rc = feed_files_inflate(opt.files, paired, opt.batch, std::max(1, opt.threads), opt.threads, opt.verbose, pipe, n_processed, pack_s, &feeder, reset_run,
+                                         inflater.get(), n_gpus == 1 && !opt.share_device);
   // (also when there was no read to wait for it; not a second time when the feed failed on this very error and has printed it)
   { std::string e; if (!index_ready(&e)) { if (!(feed_rc && ix_err_in_feed)) std::cerr << "Error: " << e << std::endl; return 1; } }
   if (feed_rc) return 1;

@@ -19,6 +19,7 @@
  *       FastqSequenceReader::fetchSequences      src/ProcessReads.cpp:3128-3267   -> kamd_pack_reads (2-bit packing of a parsed batch)
  *       BUSProcessor::processBuffer, --aa branch  src/ProcessReads.cpp:1633-1726   -> kamd_pseudoalign_aa (translated search: six comma-free
  *       (nn_to_cfc src/KmerIndex.cpp:16-138, MinCollector::intersectKmersCFC src/MinCollector.cpp:44-119)   frames per read, kamd_cfc_frames)
+ *       BUSProcessor::processBuffer, a record's class and `-n` number  src/ProcessReads.cpp:1747-1749 -> kamd_read_ecs (a second pass after kamd_ec_finalize)
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -455,6 +456,33 @@ int kamd_ec_download(kamd_ctx*, uint64_t* ec_off, uint32_t* ec_ids, uint32_t* co
  * kamd_em_run reuses the EM plan of the matrix, like a bootstrap replicate does. */
 int kamd_ec_upload(kamd_ctx*, const uint64_t* ec_off, const uint32_t* ec_ids, const uint32_t* counts, uint64_t n_ecs);
 int kamd_ec_set_counts(kamd_ctx*, const uint32_t* counts);
+
+/* ---- per-read equivalence classes: which class did an item go to ----
+ * A second, opt-in pass over a batch AFTER the classes are final.  It recomputes every item's transcript set with the per-item logic
+ * kamd_pseudoalign runs (KmerIndex::match per mate, the emptiness rules, the intersection or --union under the on-list mask, the shades, the
+ * positional filters) and looks that set up in the context's current EC result -- the one kamd_ec_finalize / kamd_ec_finalize_result /
+ * kamd_ec_download describe, or the one kamd_ec_upload installed.  d_ec[i] = the row of that result whose transcript set item i was counted
+ * under (with kamd_ec_track_order(ctx, 1): the first-occurrence id), KAMD_READ_EC_NONE when the item is not pseudoaligned, KAMD_READ_EC_FOREIGN
+ * when it has a set that the result does not hold (its batch was not part of the result).  It is what `bus -n` writes as a record's class
+ * (src/ProcessReads.cpp:1747-1749).
+ *   - d_words / d_len / max_len describe a batch exactly as for kamd_pseudoalign (paired input: an item is a pair); the batches may be cut
+ *     differently from the ones that were pseudoaligned; the options must be the ones the result was made with.
+ *   - needs an EC result: without one (nothing finalized or uploaded, or kamd_pseudoalign / kamd_ec_reset / kamd_ec_allreduce since) the call
+ *     fails with an error text.
+ *   - never changes the EC state, the counts, the tuple table or the fragment-length sample.
+ *   - the result's look-up table (16 bytes per slot, a power of two >= 2 x n_ecs slots) is built on the first call after a finalize / upload
+ *     and kept until the result is replaced; kamd_ec_set_counts keeps it.
+ *   - scratch does not grow with n_items: the batch is worked through in chunks of 65536 items (see kamd_readec.hip for the bound).
+ *   - more distinct (block, strand) pairs among a read's hits than the per-hit strand filter keeps is the error kamd_pseudoalign reports.
+ *   - runs on the context stream and synchronises it once.  out (nullable): the counts of this call and its time by HIP events. */
+#define KAMD_READ_EC_NONE    (-1)   /* the item is not pseudoaligned (no hit, empty intersection, off-list, filtered away) */
+#define KAMD_READ_EC_FOREIGN (-2)   /* the item has a set, but the context's EC result does not hold it (the batch was not part of it) */
+typedef struct { uint64_t n_items, n_mapped, n_none, n_foreign; float last_ms; } kamd_read_ecs_stats;
+int kamd_read_ecs(kamd_ctx*, const kamd_quant_opts*, const uint32_t* d_words, const uint16_t* d_len, uint64_t n_items,
+                  int32_t max_len, int32_t* d_ec /* device, [n_items] */, kamd_read_ecs_stats* out /* host, nullable */);
+/* diagnostic / tests: SETS the items per chunk of kamd_read_ecs and the entries of its first tier's per-item list (0 = the defaults, 65536 and 64),
+   and reports (all nullable) what the table build and the per-item launches of the last call took and how many of its items went to the second tier */
+int kamd_debug_read_ecs(kamd_ctx*, uint64_t chunk_items, int32_t list_cap, float* table_ms, float* items_ms, uint64_t* n_second_tier);
 
 /* ---- S3: EM ---- */
 /* Runs EMAlgorithm(counts, ...).run(n_iter, min_rounds) (src/EMAlgorithm.h:26-48,95-223) on the finalized EC result

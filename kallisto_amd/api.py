@@ -86,6 +86,15 @@ class _AaStats(C.Structure):
                 ("n_winner", C.c_uint64 * 6), ("last_translate_ms", C.c_float), ("last_match_ms", C.c_float)]
 
 
+class _ReadEcsStats(C.Structure):
+    """kamd_read_ecs_stats: what one kamd_read_ecs call found."""
+    _fields_ = [("n_items", C.c_uint64), ("n_mapped", C.c_uint64), ("n_none", C.c_uint64), ("n_foreign", C.c_uint64), ("last_ms", C.c_float)]
+
+
+READ_EC_NONE = -1      # KAMD_READ_EC_NONE: the item is not pseudoaligned
+READ_EC_FOREIGN = -2   # KAMD_READ_EC_FOREIGN: the item has a set that the context's EC result does not hold
+
+
 class BgzfMember(C.Structure):
     """kamd_bgzf_member: one BGZF member of a kamd_bgzf_inflate call (raw deflate stream at src_off of the compressed bytes -> isize bytes at dst_off)."""
     _fields_ = [("src_off", C.c_uint64), ("src_len", C.c_uint32), ("isize", C.c_uint32), ("crc32", C.c_uint32), ("reserved", C.c_uint32),
@@ -188,6 +197,8 @@ _SYMBOLS = {
     "kamd_ec_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kamd_ec_upload": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kamd_ec_set_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kamd_read_ecs": (C.c_int, [C.c_void_p, C.POINTER(QuantOpts), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(_ReadEcsStats)]),
+    "kamd_debug_read_ecs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
     "kamd_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "kamd_em_run_partitioned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
@@ -517,6 +528,24 @@ class Context:
     def pseudoalign(self, opts: QuantOpts, words, lens, n_items: int, max_len: int):
         _check(load_library().kamd_pseudoalign(self._h, C.byref(opts), words.data_ptr(), lens.data_ptr(), n_items, max_len),
                "kamd_pseudoalign")
+
+    def read_ecs(self, opts: QuantOpts, words, lens, n_items: int, max_len: int):
+        """kamd_read_ecs: per item of the batch the row of the context's finalized EC result it was counted under (READ_EC_NONE: not
+        pseudoaligned, READ_EC_FOREIGN: a set the result does not hold).  Returns (int32 device tensor [n_items], stats dict)."""
+        torch = self.torch
+        out = torch.empty(max(n_items, 1), dtype=torch.int32, device=f"cuda:{self.device}")
+        s = _ReadEcsStats()
+        _check(load_library().kamd_read_ecs(self._h, C.byref(opts), words.data_ptr(), lens.data_ptr(), n_items, max_len, out.data_ptr(), C.byref(s)),
+               "kamd_read_ecs")
+        return out[:n_items], {"n_items": int(s.n_items), "n_mapped": int(s.n_mapped), "n_none": int(s.n_none), "n_foreign": int(s.n_foreign),
+                               "ms": float(s.last_ms)}
+
+    def debug_read_ecs(self, chunk_items: int = 0, list_cap: int = 0) -> dict:
+        """kamd_debug_read_ecs: sets the items per chunk of read_ecs and the entries of its first tier's lists (0 = the defaults) and returns what the
+        table build and the per-item launches of the last read_ecs took and how many of its items went to the second tier."""
+        a, b, n = C.c_float(0), C.c_float(0), C.c_uint64(0)
+        _check(load_library().kamd_debug_read_ecs(self._h, int(chunk_items), int(list_cap), C.byref(a), C.byref(b), C.byref(n)), "kamd_debug_read_ecs")
+        return {"table_ms": float(a.value), "items_ms": float(b.value), "n_second_tier": int(n.value)}
 
     # ---- translated search (bus --aa) ----
     def cfc_frames(self, words, lens, n_reads: int, max_len: int):

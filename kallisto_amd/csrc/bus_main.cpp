@@ -13,6 +13,9 @@
 // In bulk mode all records of a sample with the same class are identical (barcode = sample, UMI = -1, count = 1), so this
 // front-end writes what `bustools sort` would make of that file: one record per (sample, class) with the number of reads
 // in `count`, ordered by barcode, then class -- the per-sample EC counts the quant path produces on the GPU anyway.
+// With -n / --num (src/ProcessReads.cpp:1747-1749) every record carries the number of its read in `flags`, so nothing collapses: after a
+// sample's classes are final its files are read once more, kamd_read_ecs names every read's class, and the records are written per read,
+// sorted by (barcode, UMI, class, flags).
 // Host code only; everything that computes runs through the C ABI.
 #include <map>
 #include <unordered_map>
@@ -61,6 +64,9 @@ void usage_bus() {
             << "                              `bustools sort` makes of the reference's file.  Either way the records are sorted by barcode and\n"
             << "                              class, and matrix.ec lists the classes that occur, numbered in order of first appearance (the\n"
             << "                              reference numbers the index's classes first; class ids are arbitrary on both sides)\n"
+            << "-n, --num                     Output number of read in flag column (one record per pseudoaligned read; implies --bus-per-read;\n"
+            << "                              the input is read twice and must be regular files; not with --aa; with --inflate=device the\n"
+            << "                              second reading inflates on the host)\n"
             << "    --verbose                 Print out progress information\n";
 }
 
@@ -78,7 +84,7 @@ int bus_main(int argc, char** argv) {
   if (argc == 2) { usage_bus(); return 0; }
   std::string index, output, technology, batch_file, val;
   std::vector<std::string> files;
-  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false, aa = false, inflate_device = false;
+  bool paired = false, verbose = false, do_union = false, no_jump = false, per_read = false, index_build_device = false, aa = false, inflate_device = false, num = false;
   int strand = 0, threads = 1;
   uint64_t batch = 4u << 20;
   for (int i = 2; i < argc; i++) {
@@ -102,8 +108,9 @@ int bus_main(int argc, char** argv) {
     else if (a == "--no-jump") no_jump = true;
     else if (a == "--bus-per-read") per_read = true;
     else if (a == "--aa") aa = true;
+    else if (a == "-n" || a == "--num") { num = true; per_read = true; }
     else if (a == "--verbose") verbose = true;
-    else if (a == "-l" || a == "--list" || a == "-b" || a == "--bam" || a == "-n" || a == "--num" || a == "--genomebam" || a == "-g" || a == "--gtf" ||
+    else if (a == "-l" || a == "--list" || a == "-b" || a == "--bam" || a == "--genomebam" || a == "-g" || a == "--gtf" ||
              a == "-c" || a == "--chromosomes" || a == "-T" || a == "--tag" || a == "--long" || a == "-P" || a == "--platform" || a == "-r" ||
              a == "--threshold" || a == "--unmapped" || a == "--inleaved" || a == "-N" || a == "--numReads" ||
              a == "--batch-barcodes" || a == "--dfk-onlist") {
@@ -120,6 +127,7 @@ int bus_main(int argc, char** argv) {
     paired = false;
     if (do_union) { std::cerr << "--union is not compatible with this mode" << std::endl; ok = false; }
     if (no_jump) { std::cerr << "--no-jump is not compatible with this mode" << std::endl; ok = false; }
+    if (num) { std::cerr << "Error: -n/--num is not available with --aa" << std::endl; ok = false; }
   }
   if (index.empty()) { std::cerr << "Error: kallisto index file missing" << std::endl; ok = false; }
   else if (stat(index.c_str(), &st) != 0) { std::cerr << "Error: kallisto index file not found " << index << std::endl; ok = false; }
@@ -172,6 +180,10 @@ int bus_main(int argc, char** argv) {
       if (ok && batch_ids.empty()) { std::cerr << "Error: Missing read files" << std::endl; ok = false; }
     }
   }
+  if (ok && num)   // the reads' numbers come from a second reading of the input
+    for (const auto& fs : batch_files)
+      for (const auto& f : fs)
+        if (ok && stat(f.c_str(), &st) == 0 && !S_ISREG(st.st_mode)) { std::cerr << "Error: -n/--num reads the input twice; " << f << " is not a regular file" << std::endl; ok = false; }
   if (!ok) { std::cerr << std::endl; usage_bus(); return 1; }
   const std::string start_time = now_string(), call = call_string(argc, argv);
   // batch_id_mapping (src/ProcessReads.h:211-223): lines with the same id share a barcode
@@ -218,9 +230,36 @@ int bus_main(int argc, char** argv) {
   // one pipeline for all samples (text rings and buffers are allocated once); the sample under way is behind these two
   uint32_t* flens = nullptr;
   uint64_t fld_used = 0;
+  // -n: the second reading of a sample.  num_records: (barcode, class of matrix.ec, number of the read) of every pseudoaligned read; row_to_ec: row of
+  // the sample's finalized result -> class of matrix.ec (filled from the sample's download); num_next: number of the next read
+  struct NumRecord { uint64_t barcode; int32_t ec; uint32_t flags; };
+  std::vector<NumRecord> num_records;
+  std::vector<int32_t> row_to_ec, h_row;
+  int32_t* d_row = nullptr; uint64_t d_row_cap = 0;
+  bool num_pass = false;
+  uint64_t num_next = 0, num_barcode = 0;
   auto run_batch = [&](int, PackedBatch& b, std::string& err) -> int {
     const bool want_fld = paired && fld_used < 10000;
     int rc = 0;
+    if (num_pass) {
+      if (b.n_items > d_row_cap) {
+        if (d_row) (void)hipFree(d_row);
+        d_row = nullptr; d_row_cap = b.n_items * 5 / 4;
+        if (hipMalloc((void**)&d_row, d_row_cap * sizeof(int32_t)) != hipSuccess) { err = "device allocation of the per-read classes failed"; d_row_cap = 0; return -100; }
+      }
+      rc = kamd_read_ecs(ctx, &qo, b.d_words, b.d_len, b.n_items, b.max_len, d_row, nullptr);
+      if (rc) { err = kamd_last_error(); return rc; }
+      h_row.resize(b.n_items);
+      if (hipMemcpy(h_row.data(), d_row, b.n_items * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) { err = "copy of the per-read classes failed"; return -100; }
+      for (uint64_t i = 0; i < b.n_items; i++) {
+        const int32_t r = h_row[i];
+        if (r == KAMD_READ_EC_NONE) continue;
+        if (r < 0 || (size_t)r >= row_to_ec.size() || row_to_ec[r] < 0) { err = "-n: read " + std::to_string(num_next + i) + " has a class the sample's result does not hold"; return -1; }
+        num_records.push_back(NumRecord{num_barcode, row_to_ec[r], (uint32_t)(num_next + i)});
+      }
+      num_next += b.n_items;
+      return 0;
+    }
     if (aa) {
       rc = kamd_pseudoalign_aa(ctx, b.d_words, b.d_len, b.n_items, b.max_len);
       if (rc) err = kamd_last_error();
@@ -251,16 +290,37 @@ int bus_main(int argc, char** argv) {
     std::vector<uint64_t> ec_off(ec.n_ecs + 1); std::vector<uint32_t> ec_ids(std::max<uint64_t>(ec.nnz, 1)), counts(std::max<uint64_t>(ec.n_ecs, 1));
     KX(kamd_ec_download(ctx, ec_off.data(), ec_ids.data(), counts.data()));
     auto& mine = per_barcode[barcode_of[sidx]];
+    if (num) row_to_ec.assign(ec.n_ecs, -1);
     for (uint64_t e = 0; e < ec.n_ecs; e++) {
       if (counts[e] == 0) continue;
       std::vector<uint32_t> key(ec_ids.begin() + ec_off[e], ec_ids.begin() + ec_off[e + 1]);
       auto it = ec_of.find(key);
       if (it == ec_of.end()) { it = ec_of.emplace(std::move(key), (int32_t)ec_of.size()).first; ec_sets.push_back(&it->first); }
+      if (num) row_to_ec[e] = it->second;
       mine[it->second] += counts[e];
       num_pseudoaligned += counts[e];
       if (ec_off[e + 1] - ec_off[e] == 1) num_unique += counts[e];
     }
+    if (num) {
+      // the sample's files once more, through the same feeder, with kamd_read_ecs in the place of kamd_pseudoalign.  The number of a read (of a pair)
+      // is its position in its own sample, from 0: in bulk mode the reference reads every sample with a reader of its own (src/ProcessReads.cpp:385-392),
+      // files on the command line as well as lines of a batch file -- what its output shows (tests/golden/bus_num)
+      num_next = 0;
+      const size_t first_record = num_records.size();
+      num_barcode = barcode_of[sidx];
+      num_pass = true;
+      uint64_t n_again = 0; double pack_again = 0.0;
+      {
+        MultiPipe pipe(1, run_batch, [] { return false; });
+        auto reset_pass = [&]() -> int { num_records.resize(first_record); num_next = 0; return 0; };
+        if (feed_files_inflate(batch_files[sidx], paired, batch, std::max(1, threads), threads, false, pipe, n_again, pack_again, &feeder, reset_pass, nullptr, true)) return 1;
+        pipe.finish();
+        if (pipe.failed()) { std::cerr << "Error: " << pipe.error() << std::endl; return 1; }
+      }
+      num_pass = false;
+    }
   }
+  if (d_row) (void)hipFree(d_row);
   std::cerr << " done" << std::endl;
   std::cerr << "[quant] processed " << n_processed << " reads, " << num_pseudoaligned << " reads pseudoaligned";
   if (num_pseudoaligned == 0) std::cerr << "[~warn] no reads pseudoaligned.";
@@ -275,8 +335,14 @@ int bus_main(int argc, char** argv) {
     of.write("BUS\0", 4);
     of.write((const char*)&version, 4); of.write((const char*)&bclen, 4); of.write((const char*)&umilen, 4); of.write((const char*)&tlen, 4);
     of.write(text.data(), tlen);
+    if (num) {   // one record per pseudoaligned read, the read's number in `flags`; the order `bustools sort` gives
+      std::sort(num_records.begin(), num_records.end(), [](const NumRecord& a, const NumRecord& b) {
+        return a.barcode != b.barcode ? a.barcode < b.barcode : (a.ec != b.ec ? a.ec < b.ec : a.flags < b.flags); });
+      for (const NumRecord& n : num_records) { BusRecord r{n.barcode, ~0ULL, n.ec, 1u, n.flags, 0}; of.write((const char*)&r, sizeof r); }
+    }
     for (const auto& bcs : per_barcode)
       for (const auto& ec_n : bcs.second) {
+        if (num) break;
         uint64_t left = ec_n.second;
         while (left) {   // `count` is 32 bits; --bus-per-read: one record per read, as BUSProcessor::processBuffer writes them (src/ProcessReads.cpp:1600-1640)
           BusRecord r{bcs.first, ~0ULL, ec_n.first, per_read ? 1u : (uint32_t)std::min<uint64_t>(left, 0xFFFFFFFFu), 0, 0};

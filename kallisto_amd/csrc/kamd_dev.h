@@ -9,6 +9,8 @@
 //   kamd_aa.hip      translated search: the six comma-free frames of a read, match and frame rule (kamd_cfc_frames, kamd_pseudoalign_aa); per-item logic in kamd_aa.h
 //   kamd_inflate.hip BGZF members inflated on the device (k_bgzf_inflate, CRC-32), newline counts and the cut of whole records (kamd_bgzf_inflate, kamd_text_cut);
 //                    decoder in kamd_inflate.h
+//   kamd_readec.hip  per-read equivalence classes: a second pass that looks every item's transcript set up in the finalized result (kamd_read_ecs);
+//                    table and look-up in kamd_readec.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -340,6 +342,13 @@ struct kamd_ctx {
   hipEvent_t aa_ev[3] = {nullptr, nullptr, nullptr};
   // device-side inflate (kamd_inflate.hip): the call's member list and per-member {reason, newlines}; kamd_text_cut's per-chunk newline counts and its result
   DBuf inf_members, inf_res, txt_counts, txt_res;
+  // per-read classes (kamd_readec.hip): the look-up table of the finalized result and the generation it was built for, the per-item lists of a chunk's
+  // two tiers, the items of a chunk that go to the second tier, the counters of a call
+  DBuf rec_table, rec_scratch, rec_big_scratch, rec_big_items, rec_ctr;
+  u64 rec_table_gen = 0, rec_table_cap = 0, rec_chunk = 0, rec_second = 0;   // (rec_table_cap == 0: no table; rec_chunk == 0: the default chunk; items of the last call's second tier)
+  int rec_small_cap = 0;   // (0: the default capacity of the first tier's lists)
+  hipEvent_t rec_ev[3] = {nullptr, nullptr, nullptr};
+  float rec_table_ms = 0.f, rec_items_ms = 0.f;
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 

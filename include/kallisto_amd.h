@@ -20,6 +20,8 @@
  *       BUSProcessor::processBuffer, --aa branch  src/ProcessReads.cpp:1633-1726   -> kamd_pseudoalign_aa (translated search: six comma-free
  *       (nn_to_cfc src/KmerIndex.cpp:16-138, MinCollector::intersectKmersCFC src/MinCollector.cpp:44-119)   frames per read, kamd_cfc_frames)
  *       BUSProcessor::processBuffer, a record's class and `-n` number  src/ProcessReads.cpp:1747-1749 -> kamd_read_ecs (a second pass after kamd_ec_finalize)
+ *       BUSProcessor::processBuffer, barcode / UMI / sequence of a technology  src/ProcessReads.cpp:1486-1627, 1739-1746 -> kamd_bus_split, kamd_bus_records
+ *       (the technology table and ParseTechnology, src/main.cpp:1283-1408, 778-870 -> kamd_bus_layout_parse)
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -120,7 +122,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 8
+#define KAMD_ABI_VERSION 9
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -483,6 +485,65 @@ int kamd_read_ecs(kamd_ctx*, const kamd_quant_opts*, const uint32_t* d_words, co
 /* diagnostic / tests: SETS the items per chunk of kamd_read_ecs and the entries of its first tier's per-item list (0 = the defaults, 65536 and 64),
    and reports (all nullable) what the table build and the per-item launches of the last call took and how many of its items went to the second tier */
 int kamd_debug_read_ecs(kamd_ctx*, uint64_t chunk_items, int32_t list_cap, float* table_ms, float* items_ms, uint64_t* n_second_tier);
+
+/* ---- barcode / UMI technologies (`bus -x <technology>`): device-side BUS records ----
+ * What BUSProcessor::processBuffer does with a read set in front of match() and for its record behind it (src/ProcessReads.cpp:1486-1627,
+ * 1739-1746), for a technology without tag sequence, --paired, --batch-barcodes and batch mode.  A technology is a LAYOUT: up to
+ * KAMD_BUS_MAX_PARTS barcode parts and as many UMI parts, each (file, start, stop) like BUSOptionSubstr (stop == 0: to the end of the read;
+ * file == -1 on the first part: the field is absent, n = 1), exactly one sequence part, n_files in {1, 2}.  The rules (kamd_bustag.h restates them):
+ *   - a part outside its read (l < start + len) or empty drops the read set: it is not counted as processed.  The UMI is checked first.
+ *   - a field is encoded as stringToBinary does (src/BUSData.cpp:8-36) over the first min(len, 32) bases; a base that is not ACGT takes code 2 and
+ *     counts as an N; flags = f_barcode | f_umi << 8.  Absent UMI: ~0, and f_umi repeats f_barcode (the reference shifts in what `f` last held);
+ *     absent barcode: 0 of length 16.
+ *   - the sequence is bases [start, stop ? stop : l), clamped to the read; l <= start is an empty read that is processed and never pseudoaligned.
+ *     (The reference reads past the string there: identical whenever l >= max(start + 1, stop).)
+ *   - deviations: an IUPAC letter other than N in a tag is an N here (packed records only know "ACGT or not"); a layout whose parts are all
+ *     fixed and sum to more than 32 bases is refused (the reference truncates).
+ * The calls in order, per batch: kamd_bus_split -> kamd_pseudoalign on the cut batch (single-end options: paired 0, fld 200, sd 20,
+ * single_overhang 1, the technology's strand) -> kamd_ec_finalize -> kamd_read_ecs on the cut batch -> kamd_bus_records.
+ *
+ * kamd_bus_layout_parse: `technology` is a name (10XV2, 10XV3, VISIUM, SURECELL, DROPSEQ, INDROPSV1, INDROPSV2, CELSEQ, CELSEQ2, SPLIT-SEQ,
+ * SCRBSEQ, BDWTA, VASA-SEQ; any case) or a custom "bc:umi:seq" string of comma-separated triples, checked as ParseTechnology does
+ * (src/main.cpp:778-870, its messages).  *default_strand (nullable): the strand the reference gives the technology when no strand option is
+ * passed (0 unstranded, 1 --fr-stranded, 2 --rf-stranded).  Refused with a reason: technologies of three or four files (10XV1, INDROPSV3,
+ * SMARTSEQ2, SMARTSEQ3), two sequence parts (STORM-SEQ), BULK (kamd_pseudoalign takes whole reads), a UMI in the FASTQ comment (RX), more than
+ * KAMD_BUS_MAX_PARTS parts, fixed fields over 32 bases.  Returns 0, or -1 with the text in err (nullable, err_cap bytes incl. the NUL).  Host only. */
+#define KAMD_BUS_MAX_PARTS 8
+#define KAMD_BUS_FAKE_BARCODE_LEN 16   /* BUSFORMAT_FAKE_BARCODE_LEN */
+typedef struct { int32_t file, start, stop; } kamd_bus_substr;
+typedef struct {
+  int32_t n_files;                 /* records per item: 1 or 2 */
+  int32_t n_bc, n_umi;             /* parts in use, 1 .. KAMD_BUS_MAX_PARTS */
+  int32_t reserved;
+  kamd_bus_substr bc[KAMD_BUS_MAX_PARTS], umi[KAMD_BUS_MAX_PARTS], seq;
+} kamd_bus_layout;
+typedef struct { uint64_t barcode, umi; uint32_t flags; uint16_t bc_len, umi_len; } kamd_bus_tag;   /* 24 bytes; *_len: bases of the field in the read (may exceed 32) */
+typedef struct { uint64_t barcode, umi; int32_t ec; uint32_t count, flags, pad; } kamd_bus_record; /* 32 bytes: BUSData (src/BUSData.h) */
+typedef struct {
+  uint64_t n_items, n_valid, n_dropped_umi, n_dropped_bc;
+  uint64_t bc_len_hist[33], umi_len_hist[33];   /* the reference's bc_len[] / umi_len[]: UMI lengths of every item whose UMI is there (absent UMI: length 1 for every item), barcode lengths of the surviving items */
+  int32_t max_seq_len;                          /* longest cut sequence of the surviving items */
+  float last_ms;                                /* the call's kernels by HIP events */
+} kamd_bus_split_stats;
+int kamd_bus_layout_parse(const char* technology, kamd_bus_layout* out, int32_t* default_strand, char* err, size_t err_cap);
+/* The bound a caller sizes d_seq_words / d_seq_len with: no cut of a batch with reads of up to max_len bases is longer (at least 1). */
+int32_t kamd_bus_seq_max_len(const kamd_bus_layout*, int32_t max_len);
+/* kamd_bus_split: one batch of items (an item = n_files consecutive records at max_len, as kamd_fastq_* and kamd_pack_reads emit them; fewer than
+ * 2^32 items) -> its surviving items, compact and in input order: compact item j is the j-th item that is not dropped.
+ *   d_tags [n_items]       tag of compact item j            d_src [n_items]   input item of compact item j
+ *   d_seq_words / d_seq_len   a single-end batch of the cut sequences at seq_max_len (>= kamd_bus_seq_max_len), record stride
+ *                             kamd_packed_record_words(seq_max_len), every word written as kamd_pack_reads_host writes the substring
+ * Only the first n_valid entries of the outputs are written.  Three kernels (count, scan of the block counts, scatter) and the repack; no host
+ * round trip but the final read of the statistics (out, nullable), for which the context stream is synchronised once.  Scratch: 4 bytes per
+ * 256 items.  Touches neither the EC state, the counts, the tuple table nor the fragment-length sample. */
+int kamd_bus_split(kamd_ctx*, const kamd_bus_layout*, const uint32_t* d_words, const uint16_t* d_len, uint64_t n_items, int32_t max_len,
+                   kamd_bus_tag* d_tags, uint32_t* d_src, uint32_t* d_seq_words, uint16_t* d_seq_len, int32_t seq_max_len,
+                   kamd_bus_split_stats* out);
+/* kamd_bus_records: the tags of a cut batch and the rows kamd_read_ecs named for it -> 32-byte BUS records {barcode, UMI, ec = row, count = 1,
+ * flags, pad = 0} of the items with d_ec >= 0, in order (stable compaction; KAMD_READ_EC_NONE is skipped).  *n_out (host): records written,
+ * at most n.  A KAMD_READ_EC_FOREIGN row anywhere is an error (-4, with a text) and *n_out = 0: the batch was not part of the finalized result.
+ * Same scratch, stream and guarantees as kamd_bus_split. */
+int kamd_bus_records(kamd_ctx*, const kamd_bus_tag* d_tags, const int32_t* d_ec, uint64_t n, kamd_bus_record* d_out, uint64_t* n_out);
 
 /* ---- S3: EM ---- */
 /* Runs EMAlgorithm(counts, ...).run(n_iter, min_rounds) (src/EMAlgorithm.h:26-48,95-223) on the finalized EC result

@@ -63,7 +63,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 8   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 9   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -93,6 +93,56 @@ class _ReadEcsStats(C.Structure):
 
 READ_EC_NONE = -1      # KAMD_READ_EC_NONE: the item is not pseudoaligned
 READ_EC_FOREIGN = -2   # KAMD_READ_EC_FOREIGN: the item has a set that the context's EC result does not hold
+
+
+BUS_MAX_PARTS = 8   # KAMD_BUS_MAX_PARTS
+BUS_TAG_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("flags", "<u4"), ("bc_len", "<u2"), ("umi_len", "<u2")])            # kamd_bus_tag
+BUS_RECORD_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("ec", "<i4"), ("count", "<u4"), ("flags", "<u4"), ("pad", "<u4")])   # kamd_bus_record = BUSData
+
+
+class BusSubstr(C.Structure):
+    """kamd_bus_substr: (file, start, stop) of one part of a field; stop == 0: to the end of the read; file == -1: the field is absent."""
+    _fields_ = [("file", C.c_int32), ("start", C.c_int32), ("stop", C.c_int32)]
+
+
+class BusLayout(C.Structure):
+    """kamd_bus_layout: where barcode, UMI and sequence lie in the reads of a technology (`bus -x`)."""
+    _fields_ = [("n_files", C.c_int32), ("n_bc", C.c_int32), ("n_umi", C.c_int32), ("reserved", C.c_int32),
+                ("bc", BusSubstr * BUS_MAX_PARTS), ("umi", BusSubstr * BUS_MAX_PARTS), ("seq", BusSubstr)]
+
+    @classmethod
+    def parse(cls, technology: str):
+        """kamd_bus_layout_parse: a technology name (10XV3, SURECELL, ...; any case) or a custom "bc:umi:seq" string -> (layout, the strand the
+        reference gives the technology by default: 0 unstranded, 1 --fr-stranded, 2 --rf-stranded).  Raises KallistoAmdError with the parser's text."""
+        L, strand, err = cls(), C.c_int32(0), C.create_string_buffer(512)
+        if load_library().kamd_bus_layout_parse(technology.encode(), C.byref(L), C.byref(strand), err, len(err)) != 0:
+            raise KallistoAmdError(f"technology {technology!r}: {err.value.decode(errors='replace')}")
+        return L, int(strand.value)
+
+    def parts(self, which: str):
+        a, n = (self.bc, self.n_bc) if which == "bc" else (self.umi, self.n_umi)
+        return [(a[i].file, a[i].start, a[i].stop) for i in range(n)]
+
+    def seq_max_len(self, max_len: int) -> int:
+        """kamd_bus_seq_max_len: no cut sequence of a batch with reads of up to max_len bases is longer."""
+        return int(load_library().kamd_bus_seq_max_len(C.byref(self), int(max_len)))
+
+    def header_lens(self, bc_len_hist, umi_len_hist):
+        """(bclen, umilen) of the BUS header: the layout's fixed sums, or, where a part is open-ended or the field absent, the modes of the length
+        histograms of the run (the first of equal bins; src/main.cpp:2472-2496)."""
+        out = []
+        for parts, hist in ((self.parts("bc"), bc_len_hist), (self.parts("umi"), umi_len_hist)):
+            if parts[0][0] >= 0 and all(b != 0 for _, _, b in parts):
+                out.append(sum(b - a for _, a, b in parts))
+            else:
+                out.append(int(np.argmax(np.asarray(hist))))
+        return tuple(out)
+
+
+class _BusSplitStats(C.Structure):
+    """kamd_bus_split_stats"""
+    _fields_ = [("n_items", C.c_uint64), ("n_valid", C.c_uint64), ("n_dropped_umi", C.c_uint64), ("n_dropped_bc", C.c_uint64),
+                ("bc_len_hist", C.c_uint64 * 33), ("umi_len_hist", C.c_uint64 * 33), ("max_seq_len", C.c_int32), ("last_ms", C.c_float)]
 
 
 class BgzfMember(C.Structure):
@@ -199,6 +249,11 @@ _SYMBOLS = {
     "kamd_ec_set_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kamd_read_ecs": (C.c_int, [C.c_void_p, C.POINTER(QuantOpts), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.POINTER(_ReadEcsStats)]),
     "kamd_debug_read_ecs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64)]),
+    "kamd_bus_layout_parse": (C.c_int, [C.c_char_p, C.POINTER(BusLayout), C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "kamd_bus_seq_max_len": (C.c_int32, [C.POINTER(BusLayout), C.c_int32]),
+    "kamd_bus_split": (C.c_int, [C.c_void_p, C.POINTER(BusLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_int32, C.POINTER(_BusSplitStats)]),
+    "kamd_bus_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kamd_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "kamd_em_run_partitioned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
@@ -270,6 +325,16 @@ def load_library():
 def _check(rc: int, what: str):
     if rc != 0:
         raise KallistoAmdError(f"{what} failed ({rc}): {load_library().kamd_last_error().decode(errors='replace')}")
+
+
+def bus_tags_numpy(tags) -> np.ndarray:
+    """the int64 [n, 3] tensor of Context.bus_split -> a host array of BUS_TAG_DTYPE"""
+    return np.ascontiguousarray(tags.cpu().numpy()).reshape(-1).view(BUS_TAG_DTYPE)
+
+
+def bus_records_numpy(records) -> np.ndarray:
+    """the int64 [n, 4] tensor of Context.bus_records -> a host array of BUS_RECORD_DTYPE (the 32-byte records of a BUS file)"""
+    return np.ascontiguousarray(records.cpu().numpy()).reshape(-1).view(BUS_RECORD_DTYPE)
 
 
 def packed_record_words(max_len: int) -> int:
@@ -546,6 +611,39 @@ class Context:
         a, b, n = C.c_float(0), C.c_float(0), C.c_uint64(0)
         _check(load_library().kamd_debug_read_ecs(self._h, int(chunk_items), int(list_cap), C.byref(a), C.byref(b), C.byref(n)), "kamd_debug_read_ecs")
         return {"table_ms": float(a.value), "items_ms": float(b.value), "n_second_tier": int(n.value)}
+
+    # ---- barcode / UMI technologies (bus -x <technology>) ----
+    def bus_split(self, layout: BusLayout, words, lens, n_items: int, max_len: int, seq_max_len: int | None = None) -> dict:
+        """kamd_bus_split: a batch of items (layout.n_files consecutive records each) -> its surviving items, compact and in input order.  Returns
+        tags (int64 [n_valid, 3]: kamd_bus_tag, see bus_tags_numpy), src (int32 [n_valid]: the input item), the cut sequences as a single-end batch
+        (seq_words, seq_len, n_valid, seq_max_len: what pseudoalign / read_ecs take) and stats (drops, length histograms, ms)."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        if seq_max_len is None:
+            seq_max_len = layout.seq_max_len(max_len)
+        n = max(int(n_items), 1)
+        tags = torch.empty((n, 3), dtype=torch.int64, device=dev)
+        src = torch.empty(n, dtype=torch.int32, device=dev)
+        seq_words = torch.empty(n * packed_record_words(seq_max_len), dtype=torch.int32, device=dev)
+        seq_len = torch.empty(n, dtype=torch.int16, device=dev)
+        st = _BusSplitStats()
+        _check(load_library().kamd_bus_split(self._h, C.byref(layout), words.data_ptr(), lens.data_ptr(), int(n_items), int(max_len), tags.data_ptr(), src.data_ptr(),
+                                             seq_words.data_ptr(), seq_len.data_ptr(), int(seq_max_len), C.byref(st)), "kamd_bus_split")
+        nv = int(st.n_valid)
+        stats = {"n_items": int(st.n_items), "n_valid": nv, "n_dropped_umi": int(st.n_dropped_umi), "n_dropped_bc": int(st.n_dropped_bc),
+                 "bc_len_hist": [int(x) for x in st.bc_len_hist], "umi_len_hist": [int(x) for x in st.umi_len_hist], "max_seq_len": int(st.max_seq_len),
+                 "ms": float(st.last_ms)}
+        return {"tags": tags[:nv], "src": src[:nv], "seq_words": seq_words[:nv * packed_record_words(seq_max_len)], "seq_len": seq_len[:nv], "n_valid": nv,
+                "seq_max_len": int(seq_max_len), "stats": stats}
+
+    def bus_records(self, tags, d_ec, n: int):
+        """kamd_bus_records: the tags of a cut batch and the rows read_ecs named for it -> the BUS records of the items with a row, in order, as an
+        int64 device tensor [n_out, 4] (kamd_bus_record: see bus_records_numpy).  A READ_EC_FOREIGN row raises."""
+        torch = self.torch
+        out = torch.empty((max(int(n), 1), 4), dtype=torch.int64, device=f"cuda:{self.device}")
+        n_out = C.c_uint64(0)
+        _check(load_library().kamd_bus_records(self._h, tags.data_ptr(), d_ec.data_ptr(), int(n), out.data_ptr(), C.byref(n_out)), "kamd_bus_records")
+        return out[:int(n_out.value)]
 
     # ---- translated search (bus --aa) ----
     def cfc_frames(self, words, lens, n_reads: int, max_len: int):

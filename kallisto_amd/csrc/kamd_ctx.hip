@@ -157,6 +157,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   if (c->ev_fin1) (void)hipEventDestroy(c->ev_fin1);
   for (hipEvent_t e : c->aa_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->rec_ev) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->bus_ev) if (e) (void)hipEventDestroy(e);
   if (c->ev_ab0) (void)hipEventDestroy(c->ev_ab0);
   if (c->ev_ab1) (void)hipEventDestroy(c->ev_ab1);
   if (c->em_stream) (void)hipStreamDestroy(c->em_stream);
@@ -193,7 +194,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
                   &c->em_segoff, &c->em_segt, &c->em_partial, &c->em_a0, &c->em_a1, &c->em_single, &c->em_actflag, &c->em_actpos, &c->em_active, &c->pt_label, &c->pt_flag, &c->pt_len,
                   &c->pt_rowpos, &c->pt_nnzpos, &c->pt_off, &c->pt_ids, &c->pt_counts, &c->pt_wcounts, &c->pt_hist, &c->pt_ck_alpha,
                   &c->pt_ck_a, &c->fq_tiles, &c->fq_nlpos[0], &c->fq_nlpos[1], &c->fq_recs, &c->fq_res, &c->fq_words, &c->fq_len, &c->aa_frames, &c->aa_flen, &c->aa_scratch, &c->aa_offlist, &c->aa_ctr, &c->inf_members, &c->inf_res, &c->txt_counts, &c->txt_res,
-                  &c->rec_table, &c->rec_scratch, &c->rec_big_scratch, &c->rec_big_items, &c->rec_ctr})
+                  &c->rec_table, &c->rec_scratch, &c->rec_big_scratch, &c->rec_big_items, &c->rec_ctr, &c->bus_blk, &c->bus_ctr})
     b->release();
   delete c;
 }

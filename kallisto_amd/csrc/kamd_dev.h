@@ -11,6 +11,8 @@
 //                    decoder in kamd_inflate.h
 //   kamd_readec.hip  per-read equivalence classes: a second pass that looks every item's transcript set up in the finalized result (kamd_read_ecs);
 //                    table and look-up in kamd_readec.h
+//   kamd_bus.hip     barcode / UMI technologies: tags, drops and the cut sequence of every item, compacted (kamd_bus_split), and the 32-byte BUS records
+//                    of a cut batch (kamd_bus_records); per-item rules in kamd_bustag.h, the layout parser in kamd_bus.cpp
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -349,6 +351,9 @@ struct kamd_ctx {
   int rec_small_cap = 0;   // (0: the default capacity of the first tier's lists)
   hipEvent_t rec_ev[3] = {nullptr, nullptr, nullptr};
   float rec_table_ms = 0.f, rec_items_ms = 0.f;
+  // barcode / UMI technologies (kamd_bus.hip): the survivors per block of 256 items (scanned in place), the counters of a call
+  DBuf bus_blk, bus_ctr;
+  hipEvent_t bus_ev[2] = {nullptr, nullptr};
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 

@@ -165,6 +165,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   if (c->em_ev_fork) (void)hipEventDestroy(c->em_ev_fork);
   if (c->em_ev_join) (void)hipEventDestroy(c->em_ev_join);
   if (c->em_pin) (void)hipHostFree(c->em_pin);
+  if (c->plan_pin) (void)hipHostFree(c->plan_pin);
   if (c->state_pin) (void)hipHostFree(c->state_pin);
   c->em_clk.release();
   if (c->hy_giant_stream) { (void)hipStreamSynchronize(c->hy_giant_stream); (void)hipStreamDestroy(c->hy_giant_stream); }

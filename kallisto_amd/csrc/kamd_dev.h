@@ -318,6 +318,7 @@ struct kamd_ctx {
   hipStream_t em_stream = nullptr;
   hipStream_t em_side_stream = nullptr; hipEvent_t em_ev_fork = nullptr, em_ev_join = nullptr;   // component-local EM: the small size class runs beside the large one
   void* em_pin = nullptr; size_t em_pin_bytes = 0;   // component-local EM: pinned, mapped host memory (change counts the kernels publish, result staging)
+  void* plan_pin = nullptr; size_t plan_pin_bytes = 0;   // component-local EM: pinned staging of the plan's size read-backs (a pageable destination is staged by the runtime)
   DBuf em_clk;                                       // diagnostic phase clocks (KAMD_EM_CLK)
   // hybrid EM (components beyond a workgroup's LDS beside the LDS form): the two sub-matrices, the streamed plan's arenas, its vectors
   DBuf hy_sub, hy_a, hy_b, hy_x, hy_maps;

@@ -1083,6 +1083,7 @@ struct EmSellDev {
   const u32* row_base; const u32* tr_base; const u32* rslice_base; const u32* cslice_base; const u64* rell_base; const u64* cell_base;
   const u32* rdesc; const u32* cdesc; const uint16_t* rell; const uint16_t* cell;
   const u64* cw; const double* single; const double* eff;
+  const u32* grec;   // the six bases of group g and of g + 1 as ONE record of 16 words (k_sell_group_rec): a launch fetches it with one scalar load
 };
 constexpr int EMS_MAX_BLOCK = 1024;
 // sum over the lane's entries of one slice; e: the lane's first 64-bit word of four u16 indices (kamd_em_sell.h: word q of the lane at e + q * 64)
@@ -1131,22 +1132,133 @@ __device__ __forceinline__ double ems_slice_sum(const u64* e, u32 width, const d
   if constexpr (EXP != 0) { if (sink == 0xFFFFFFFFu) S += 1.0; }
   return S;
 }
+// ---- a group's tables, global memory -> LDS, at the start of a launch ------------------------------------------------------------------
+// The tables are small (80-110 KB for a group of ~9 300 entries) and sit in L2 after the first launch of a run: what they cost is round
+// trips, not bytes.  So a launch fetches them with few, wide loads that are all in flight before the first wait: the group's bases (one
+// record, a scalar load issued ahead of the previous chunk's stop check), then ONE batch of vector loads -- the first TR trips of
+// every table -- whose values wait in registers while the stop check runs, then the stores to LDS.  What a batch does not cover (groups on small workgroups)
+// follows in batches of the same shape.
+struct EmsBases { u32 r0, nR, t0, nT, rs0, nrs, cs0, ncs; u64 re0, ce0; u32 nru, ncu; };
+constexpr int EMS_GREC_WORDS = 16;   // r0, nR, t0, nT | rs0, nrs, cs0, ncs | re0 (lo, hi), ce0 (lo, hi) | nru, ncu, -, -
+__device__ __forceinline__ EmsBases ems_bases(const EmSellDev& P, u32 g) {
+  const uint4* r = reinterpret_cast<const uint4*>(P.grec + (size_t)g * EMS_GREC_WORDS);
+  const uint4 q0 = r[0], q1 = r[1], q2 = r[2], q3 = r[3];
+  EmsBases B;
+  B.r0 = q0.x; B.nR = q0.y; B.t0 = q0.z; B.nT = q0.w;
+  B.rs0 = q1.x; B.nrs = q1.y; B.cs0 = q1.z; B.ncs = q1.w;
+  B.re0 = (u64)q2.x | ((u64)q2.y << 32); B.ce0 = (u64)q2.z | ((u64)q2.w << 32);
+  B.nru = q3.x; B.ncu = q3.y;
+  return B;
+}
+__global__ void k_sell_group_rec(EmSellDev P, u32 n_groups, u32* grec) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n_groups) return;
+  const u32 r0 = P.row_base[g], t0 = P.tr_base[g], rs0 = P.rslice_base[g], cs0 = P.cslice_base[g];
+  const u64 re0 = P.rell_base[g], ce0 = P.cell_base[g];
+  uint4* r = reinterpret_cast<uint4*>(grec + (size_t)g * EMS_GREC_WORDS);
+  r[0] = make_uint4(r0, P.row_base[g + 1] - r0, t0, P.tr_base[g + 1] - t0);
+  r[1] = make_uint4(rs0, P.rslice_base[g + 1] - rs0, cs0, P.cslice_base[g + 1] - cs0);
+  r[2] = make_uint4((u32)re0, (u32)(re0 >> 32), (u32)ce0, (u32)(ce0 >> 32));
+  r[3] = make_uint4((u32)(P.rell_base[g + 1] - re0), (u32)(P.cell_base[g + 1] - ce0), 0u, 0u);
+}
+// A slice occupies 2 * SELL_META_WORDS + quad_width(width) * SELL_LANES u16 (kamd_em_sell.h), so every group's stream starts and ends
+// on a multiple of 128 entries of an array that is carved out at a 256-byte boundary: 16-byte loads of eight indices need no head or tail.
+static_assert((2 * kamd_em_sell::SELL_META_WORDS) % 8 == 0 && (4 * kamd_em_sell::SELL_LANES) % 8 == 0, "index streams are fetched eight entries at a time");
+struct EmsLds { double* al; double* a; double* single; double* eff; u64* cw; u32* rdesc; u32* cdesc; uint16_t* rell; uint16_t* cell; };
+// TR: trips of a batch -- two where the kernel has 128 registers, one in the forms held to 64
+template <int TR> struct EmsStage {
+  double al[TR], a[TR], single[TR], eff[TR];
+  u64 cw[TR], rd, cd;
+  uint4 re[TR], ce[TR];
+};
+// (a lane beyond the end of a table loads the table's first element: no branch around a load, the value is not stored.  A group without
+// any component has empty tables, n == 0: the load then reads at the table's base what follows the previous group -- the next group's first
+// element or, behind the last group, the slack every array of the plan and of the state is carved with: 8 bytes behind the 8-byte tables and
+// the descriptors, 16 behind the streams)
+template <class T> __device__ __forceinline__ T ems_ld(const T* p, u32 i, u32 n) { return p[i < n ? i : 0u]; }
+// eight indices of a stream; a padding entry (SELL_PAD) becomes the index of the zero slot.  Halves: + 1 turns SELL_PAD into 0, min(.., 1) - 1
+// into the mask 0xFFFF.  (Not a minimum against the zero slot: the metadata words of a slice hold segment ids of the OTHER direction's range.)
+__device__ __forceinline__ u32 ems_unpad2(u32 w, u32 zz) {
+  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+  const us2 one = {1, 1};
+  const us2 m = __builtin_elementwise_min((us2)(__builtin_bit_cast(us2, w) + one), one) - one;
+  const u32 mm = __builtin_bit_cast(u32, m);
+  return (w & ~mm) | (zz & mm);
+}
+__device__ __forceinline__ void ems_put8(uint16_t* dst, u32 i, uint4 v, u32 zero) {   // (the streams are 8-byte aligned in LDS, not 16)
+  const u32 zz = zero * 0x00010001u;
+  u64* d = reinterpret_cast<u64*>(dst) + 2 * (size_t)i;
+  d[0] = (u64)ems_unpad2(v.x, zz) | ((u64)ems_unpad2(v.y, zz) << 32);
+  d[1] = (u64)ems_unpad2(v.z, zz) | ((u64)ems_unpad2(v.w, zz) << 32);
+}
+// trips [trip0, trip0 + TR) of every table: all loads first
+template <int TR> __device__ __forceinline__ void ems_stage_issue(const EmSellDev& P, const EmsBases& B, const double* alpha, const double* a, u32 tid, u32 nthr, u32 trip0, EmsStage<TR>& S) {
+  const uint4* re = reinterpret_cast<const uint4*>(P.rell + B.re0);
+  const uint4* ce = reinterpret_cast<const uint4*>(P.cell + B.ce0);
+#pragma unroll
+  for (int u = 0; u < TR; u++) {
+    const u32 i = (trip0 + (u32)u) * nthr + tid;
+    S.re[u] = ems_ld(re, i, B.nru >> 3); S.ce[u] = ems_ld(ce, i, B.ncu >> 3);
+  }
+#pragma unroll
+  for (int u = 0; u < TR; u++) {
+    const u32 i = (trip0 + (u32)u) * nthr + tid;
+    S.al[u] = ems_ld(alpha + B.t0, i, B.nT); S.a[u] = ems_ld(a + B.t0, i, B.nT);
+    S.single[u] = ems_ld(P.single + B.t0, i, B.nT); S.eff[u] = ems_ld(P.eff + B.t0, i, B.nT);
+    S.cw[u] = ems_ld(P.cw + B.r0, i, B.nR);
+  }
+  // (one trip of descriptors to TR of the others: a slice has one descriptor and at least 128 indices)
+  const u32 i = (trip0 / TR) * nthr + tid;
+  S.rd = ems_ld(reinterpret_cast<const u64*>(P.rdesc) + B.rs0, i, B.nrs); S.cd = ems_ld(reinterpret_cast<const u64*>(P.cdesc) + B.cs0, i, B.ncs);
+}
+template <int TR> __device__ __forceinline__ void ems_stage_store(const EmsBases& B, const EmsLds& L, int clamp, u32 tid, u32 nthr, u32 trip0, const EmsStage<TR>& S) {
+#pragma unroll
+  for (int u = 0; u < TR; u++) {
+    const u32 i = (trip0 + (u32)u) * nthr + tid;
+    if (i < B.nT) {
+      double al = S.al[u], av = S.a[u];
+      if (clamp && al < 1e-7 / 10.0) { al = 0.0; av = 0.0; }   // the final round reads alpha < alpha_limit / 10 as 0 (:212-221)
+      L.al[i] = al; L.a[i] = av; L.single[i] = S.single[u]; L.eff[i] = S.eff[u];
+    }
+    if (i < B.nR) L.cw[i] = S.cw[u];
+    // streams: a padding entry becomes the index of the zero slot (metadata words never hold 0xFFFF halves)
+    if (i < (B.nru >> 3)) ems_put8(L.rell, i, S.re[u], B.nT);
+    if (i < (B.ncu >> 3)) ems_put8(L.cell, i, S.ce[u], B.nR);
+  }
+  const u32 i = (trip0 / TR) * nthr + tid;
+  if (i < B.nrs) reinterpret_cast<u64*>(L.rdesc)[i] = S.rd;
+  if (i < B.ncs) reinterpret_cast<u64*>(L.cdesc)[i] = S.cd;
+}
+// trips a group needs beyond the first batch (wave-uniform)
+template <int TR> __device__ __forceinline__ u32 ems_stage_trips(const EmsBases& B, u32 nthr) {
+  const u32 n8 = max(max(B.nT, B.nR), max(B.nru >> 3, B.ncu >> 3));
+  const u32 nd = max(B.nrs, B.ncs);
+  return max((n8 + nthr - 1) / nthr, TR * ((nd + nthr - 1) / nthr));
+}
+template <int TR> __device__ __forceinline__ void ems_stage_rest(const EmSellDev& P, const EmsBases& B, const EmsLds& L, const double* alpha, const double* a, int clamp, u32 tid, u32 nthr) {
+  const u32 trips = ems_stage_trips<TR>(B, nthr);
+  for (u32 t = TR; t < trips; t += TR) {
+    EmsStage<TR> S;
+    ems_stage_issue(P, B, alpha, a, tid, nthr, t, S);
+    ems_stage_store(B, L, clamp, tid, nthr, t, S);
+  }
+}
 // One team of NW wavefronts iterates one group out of its own piece of LDS.  WAVE_TEAM: the team is a single wavefront (several
 // teams share a workgroup), so the two hand-overs of a round -- g after the rows pass, a / alpha after the columns pass -- need no
 // block barrier: a wavefront's LDS operations complete in order, the fence only keeps the compiler from moving them.
 // alpha_in / a_in -> alpha_out / a_out (the same vectors, or the other half of a ping-pong pair: the input then stays what it was, the
 // checkpoint a speculative chunk is replayed from).  clk: diagnostic, phase clocks of every wavefront in round EMS_CLK_ROUND.
-constexpr int EMS_CLK_ROUND = 8, EMS_CLK_WORDS = 16;
-template <bool WAVE_TEAM, int EXP = 0>
-__device__ __forceinline__ void ems_group_rounds(const EmSellDev& P, u32 g, unsigned char* smem, u32 tid, u32 nthr, const double* alpha, const double* a,
+// (words 16 .. 19, k_em_sell only: clock at kernel entry, with the group's tables in LDS, at the start of round 0, and the wall clock ticks
+// from entry to round 0 -- what a launch costs a workgroup before its first round)
+constexpr int EMS_CLK_ROUND = 8, EMS_CLK_WORDS = 20;
+// B, S0: the group's bases and the first batch of its tables, in flight since the start of the kernel (ems_stage_issue)
+template <bool WAVE_TEAM, int EXP = 0, int TR = 1>
+__device__ __forceinline__ void ems_group_rounds(const EmSellDev& P, const EmsBases& B, const EmsStage<TR>& S0, unsigned char* smem, u32 tid, u32 nthr, const double* alpha, const double* a,
                                                  double* alpha_out, double* a_out, int n_rounds, int clamp, int* s_hist, long long* clk = nullptr) {
   namespace L = kamd_em_sell;
   const int lane = lane_id();
   const u32 wv = WAVE_TEAM ? 0u : (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), NW = WAVE_TEAM ? 1u : nthr >> 6;
-  const u32 r0 = P.row_base[g], nR = P.row_base[g + 1] - r0, t0 = P.tr_base[g], nT = P.tr_base[g + 1] - t0;
-  const u32 rs0 = P.rslice_base[g], nrs = P.rslice_base[g + 1] - rs0, cs0 = P.cslice_base[g], ncs = P.cslice_base[g + 1] - cs0;
-  const u64 re0 = P.rell_base[g], ce0 = P.cell_base[g];
-  const u32 nru = (u32)(P.rell_base[g + 1] - re0), ncu = (u32)(P.cell_base[g + 1] - ce0);
+  const u32 nR = B.nR, t0 = B.t0, nT = B.nT, nrs = B.nrs, ncs = B.ncs, nru = B.nru, ncu = B.ncu;
   auto team_sync = [] {
     if (WAVE_TEAM || EXP == 5) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     else __syncthreads();
@@ -1158,20 +1270,13 @@ __device__ __forceinline__ void ems_group_rounds(const EmSellDev& P, u32 g, unsi
   u64* s_cw = reinterpret_cast<u64*>(s_g + (nR + 1));
   u32* s_rdesc = reinterpret_cast<u32*>(s_cw + nR); u32* s_cdesc = s_rdesc + 2 * nrs;
   uint16_t* s_rell = reinterpret_cast<uint16_t*>(s_cdesc + 2 * ncs); uint16_t* s_cell = s_rell + ((nru + 1) & ~1u);
-  for (u32 i = tid; i < nT; i += nthr) {
-    double al = alpha[t0 + i], av = a[t0 + i];
-    if (clamp && al < 1e-7 / 10.0) { al = 0.0; av = 0.0; }   // the final round reads alpha < alpha_limit / 10 as 0 (:212-221)
-    s_al0[i] = al; s_a0[i] = av; s_single[i] = P.single[t0 + i]; s_eff[i] = P.eff[t0 + i];
-  }
-  for (u32 i = tid; i < nR; i += nthr) s_cw[i] = P.cw[r0 + i];
-  for (u32 i = tid; i < 2 * nrs; i += nthr) s_rdesc[i] = P.rdesc[2 * (u64)rs0 + i];
-  for (u32 i = tid; i < 2 * ncs; i += nthr) s_cdesc[i] = P.cdesc[2 * (u64)cs0 + i];
-  // streams: a padding entry becomes the index of the zero slot (metadata words never hold 0xFFFF halves)
-  for (u32 i = tid; i < nru; i += nthr) { const uint16_t v = P.rell[re0 + i]; s_rell[i] = v == (uint16_t)L::SELL_PAD ? (uint16_t)nT : v; }
-  for (u32 i = tid; i < ncu; i += nthr) { const uint16_t v = P.cell[ce0 + i]; s_cell[i] = v == (uint16_t)L::SELL_PAD ? (uint16_t)nR : v; }
+  const EmsLds lds{s_al0, s_a0, s_single, s_eff, s_cw, s_rdesc, s_cdesc, s_rell, s_cell};
+  ems_stage_store(B, lds, clamp, tid, nthr, 0, S0);
+  ems_stage_rest<TR>(P, B, lds, alpha, a, clamp, tid, nthr);
   if (tid == 0) { s_al0[nT] = s_a0[nT] = s_al1[nT] = s_a1[nT] = 0.0; s_g[nR] = 0.0; }
   team_sync();
   double* al = s_al0; double* av = s_a0; double* aln = s_al1; double* avn = s_a1;
+  if (clk && lane == 0) { clk[17] = clk[18] = clock64(); clk[19] = wall_clock64(); }
   for (int r = 0; r < n_rounds; r++) {
     const bool tick = clk && r == EMS_CLK_ROUND && lane == 0;
     long long w0 = 0;
@@ -1337,17 +1442,14 @@ __device__ __forceinline__ double ems_slice_sum_narrow(const u64* e, u32 width, 
   }
   return S;
 }
-template <int W, int NS>
-__device__ __forceinline__ void ems_group_rounds_reg(const EmSellDev& P, u32 g, unsigned char* smem, u32 tid, u32 nthr, const double* alpha, const double* a,
+template <int W, int NS, int TR>
+__device__ __forceinline__ void ems_group_rounds_reg(const EmSellDev& P, const EmsBases& B, const EmsStage<TR>& S0, unsigned char* smem, u32 tid, u32 nthr, const double* alpha, const double* a,
                                                      double* alpha_out, double* a_out, int n_rounds, int clamp, int* s_hist, long long* clk = nullptr) {
   namespace L = kamd_em_sell;
   constexpr bool TREE = W >= 8 || (W == 4 && NS == 2);   // (the forms that run with 128 registers, one workgroup per CU)
   const int lane = lane_id();
   const u32 wv = (u32)__builtin_amdgcn_readfirstlane((int)(tid >> 6)), NW = nthr >> 6;
-  const u32 r0 = P.row_base[g], nR = P.row_base[g + 1] - r0, t0 = P.tr_base[g], nT = P.tr_base[g + 1] - t0;
-  const u32 rs0 = P.rslice_base[g], nrs = P.rslice_base[g + 1] - rs0, cs0 = P.cslice_base[g], ncs = P.cslice_base[g + 1] - cs0;
-  const u64 re0 = P.rell_base[g], ce0 = P.cell_base[g];
-  const u32 nru = (u32)(P.rell_base[g + 1] - re0), ncu = (u32)(P.cell_base[g + 1] - ce0);
+  const u32 nR = B.nR, t0 = B.t0, nT = B.nT, nrs = B.nrs, ncs = B.ncs, nru = B.nru, ncu = B.ncu;
   // the layout kamd_em_sell::group_bytes() prices, in another order: the two gathered arrays (a, then g) come first, so that their byte
   // addresses fit 16 bits for every group of up to ~8 000 rows + transcripts (what is left of the priced bytes stays unused: alpha and
   // a are updated in place here -- the rows pass only reads a, the columns pass reads and writes a[t] / alpha[t] in the one lane that
@@ -1361,18 +1463,12 @@ __device__ __forceinline__ void ems_group_rounds_reg(const EmSellDev& P, u32 g, 
   uint16_t* s_rell = reinterpret_cast<uint16_t*>(s_cdesc + 2 * ncs); uint16_t* s_cell = s_rell + ((nru + 1) & ~1u);
   const u32 a_off = 0u, g_off = (nT + 1) * 8u;
   const bool near = g_off + (nR + 1) * 8u <= 0x10000u;   // both gathered arrays inside the first 64 KB: byte addresses fit the 16-bit entries
-  for (u32 i = tid; i < nT; i += nthr) {
-    double al = alpha[t0 + i], av = a[t0 + i];
-    if (clamp && al < 1e-7 / 10.0) { al = 0.0; av = 0.0; }   // the final round reads alpha < alpha_limit / 10 as 0 (:212-221)
-    s_al0[i] = al; s_a0[i] = av; s_single[i] = P.single[t0 + i]; s_eff[i] = P.eff[t0 + i];
-  }
-  for (u32 i = tid; i < nR; i += nthr) s_cw[i] = P.cw[r0 + i];
-  for (u32 i = tid; i < 2 * nrs; i += nthr) s_rdesc[i] = P.rdesc[2 * (u64)rs0 + i];
-  for (u32 i = tid; i < 2 * ncs; i += nthr) s_cdesc[i] = P.cdesc[2 * (u64)cs0 + i];
-  for (u32 i = tid; i < nru; i += nthr) { const uint16_t v = P.rell[re0 + i]; s_rell[i] = v == (uint16_t)L::SELL_PAD ? (uint16_t)nT : v; }
-  for (u32 i = tid; i < ncu; i += nthr) { const uint16_t v = P.cell[ce0 + i]; s_cell[i] = v == (uint16_t)L::SELL_PAD ? (uint16_t)nR : v; }
+  const EmsLds lds{s_al0, s_a0, s_single, s_eff, s_cw, s_rdesc, s_cdesc, s_rell, s_cell};
+  ems_stage_store(B, lds, clamp, tid, nthr, 0, S0);
+  ems_stage_rest<TR>(P, B, lds, alpha, a, clamp, tid, nthr);
   if (tid == 0) { s_al0[nT] = s_a0[nT] = 0.0; s_g[nR] = 0.0; }
   __syncthreads();
+  if (clk && lane == 0) clk[17] = clock64();
   // ---- this wavefront's own slices: everything that does not change from round to round goes into registers ----
   struct Own { u64 w[W]; u32 nq, seg, steps; int reach; bool has, meta, fin; };
   auto take = [&](const u32* desc, const uint16_t* ell, u32 s, u32 n_slices, u32 n_segs, u32 zero, u32 base_off) {
@@ -1421,6 +1517,7 @@ __device__ __forceinline__ void ems_group_rounds_reg(const EmSellDev& P, u32 g, 
   }
   double* const al = s_al0; double* const av = s_a0;
   const unsigned char* const lds0 = smem;
+  if (clk && lane == 0) { clk[18] = clock64(); clk[19] = wall_clock64(); }
   for (int r = 0; r < n_rounds; r++) {
     const bool tick = clk && r == EMS_CLK_ROUND && lane == 0;
     long long w0 = 0;
@@ -1538,12 +1635,20 @@ __global__ __launch_bounds__(EMS_MAX_BLOCK) __attribute__((amdgpu_waves_per_eu((
   extern __shared__ __attribute__((aligned(16))) unsigned char ems_smem[];
   __shared__ int s_hist[EML_MAX_ROUNDS];
   __shared__ int s_stop;
+  long long t_in = 0, w_in = 0;
+  if constexpr (CLK) { t_in = clock64(); w_in = wall_clock64(); }
+  // the group's loads go out before the stop check's result is known: a chunk that is skipped writes nothing, what it loaded is dropped
+  constexpr int TR = (W >= 8 || (W == 4 && NS == 2)) ? 2 : 1;
+  const EmsBases B = ems_bases(P, g_first + blockIdx.x);
+  EmsStage<TR> S0;
+  ems_stage_issue(P, B, alpha, a, threadIdx.x, blockDim.x, 0, S0);
   if (ems_prev_stopped(prev, &s_stop)) return;
   if (threadIdx.x < EML_MAX_ROUNDS) s_hist[threadIdx.x] = 0;
   __syncthreads();
   long long* my_clk = CLK ? clk + ((size_t)blockIdx.x * (EMS_MAX_BLOCK / 64) + (threadIdx.x >> 6)) * EMS_CLK_WORDS : nullptr;
-  if constexpr (W > 0) ems_group_rounds_reg<W, NS>(P, g_first + blockIdx.x, ems_smem, threadIdx.x, blockDim.x, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist, my_clk);
-  else ems_group_rounds<false, EXP>(P, g_first + blockIdx.x, ems_smem, threadIdx.x, blockDim.x, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist, my_clk);
+  if constexpr (W > 0) ems_group_rounds_reg<W, NS, TR>(P, B, S0, ems_smem, threadIdx.x, blockDim.x, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist, my_clk);
+  else ems_group_rounds<false, EXP, TR>(P, B, S0, ems_smem, threadIdx.x, blockDim.x, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist, my_clk);
+  if constexpr (CLK) { if (lane_id() == 0) { my_clk[16] = t_in; my_clk[19] -= w_in; } }
   __syncthreads();
   if (hist && (int)threadIdx.x < n_rounds && s_hist[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_hist[threadIdx.x]);
 }
@@ -1555,12 +1660,15 @@ __global__ __launch_bounds__(64 * EMS_WAVE_TEAMS) void k_em_sell_wave(EmSellDev 
   extern __shared__ __attribute__((aligned(16))) unsigned char ems_smem[];
   __shared__ int s_hist[EML_MAX_ROUNDS];
   __shared__ int s_stop;
+  const u32 team = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const u32 g = blockIdx.x * EMS_WAVE_TEAMS + team;
+  const EmsBases B = ems_bases(P, g < n_small ? g : 0u);   // (a team beyond the last group fetches group 0 and drops it)
+  EmsStage<2> S0;
+  ems_stage_issue(P, B, alpha, a, (u32)lane_id(), 64u, 0, S0);
   if (ems_prev_stopped(prev, &s_stop)) return;
   if (threadIdx.x < EML_MAX_ROUNDS) s_hist[threadIdx.x] = 0;
   __syncthreads();
-  const u32 team = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const u32 g = blockIdx.x * EMS_WAVE_TEAMS + team;
-  if (g < n_small) ems_group_rounds<true>(P, g, ems_smem + (size_t)team * team_bytes, (u32)lane_id(), 64u, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist);
+  if (g < n_small) ems_group_rounds<true, 0, 2>(P, B, S0, ems_smem + (size_t)team * team_bytes, (u32)lane_id(), 64u, alpha, a, alpha_out, a_out, n_rounds, clamp, s_hist);
   __syncthreads();
   if (hist && (int)threadIdx.x < n_rounds && s_hist[threadIdx.x]) atomicAdd(&hist[threadIdx.x], s_hist[threadIdx.x]);
 }
@@ -2015,6 +2123,15 @@ int cc_labels(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, u64 n_ecs, 
   HIPC(hipGetLastError());
   return 0;
 }
+// pinned staging for the sizes the plan reads back (what lands in it is consumed before the next read-back is queued)
+int plan_pin_ensure(kamd_ctx* c, size_t bytes) {
+  if (c->plan_pin_bytes >= bytes) return 0;
+  if (c->plan_pin) { HIPC(hipStreamSynchronize(c->stream)); HIPC(hipHostFree(c->plan_pin)); c->plan_pin = nullptr; c->plan_pin_bytes = 0; }
+  const size_t want = std::max<size_t>(bytes * 2, 64 * 1024);
+  HIPC(hipHostMalloc(&c->plan_pin, want, hipHostMallocDefault));
+  c->plan_pin_bytes = want;
+  return 0;
+}
 // The plan built on the device: component labels by the kernels the partitioned EM uses, then the steps of
 // kamd_em_local.h with scans in between.  The host only sees the per-group sizes (budget check, bases) and, for the final
 // scatter, tr_id and the singleton counts.  0 = ok (P holds the host part, *dev the device part), 1 = not applicable.
@@ -2051,10 +2168,13 @@ int em_local_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids,
   hipLaunchKernelGGL(k_eml_step<0>, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, A, n_ecs);
   hipLaunchKernelGGL(k_eml_step<1>, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, A, T);
   // the largest component, read back with the entry count below (same synchronisation)
+  if (int rc = plan_pin_ensure(c, 256)) return rc;
   CompStats cst{};
+  CompStats* const cst_pin = (CompStats*)c->plan_pin;
+  u64* const nz_pin = (u64*)((char*)c->plan_pin + 64);
   HIPC(hipMemsetAsync(c->pt_hist.p, 0, sizeof(CompStats), c->stream));
   hipLaunchKernelGGL(k_comp_stats, dim3(std::min<unsigned>(grid_for(T, BLOCK), COMP_STATS_BLOCKS)), dim3(BLOCK), 0, c->stream, A.c_nnz, A.c_rows, A.c_tr, T, (u32*)c->pt_hist.p);
-  HIPC(hipMemcpyAsync(&cst, c->pt_hist.p, sizeof(CompStats), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(cst_pin, c->pt_hist.p, sizeof(CompStats), hipMemcpyDeviceToHost, c->stream));
   u64 NZ = 0;
   u32 ng = 0;
   P->n_small = 0;
@@ -2063,10 +2183,11 @@ int em_local_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids,
     hipLaunchKernelGGL(k_eml_step<9>, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, A, T);
     if (int rc = exclusive_scan(c, A.c_small, T, (u64*)(tb + o_cum), (u64*)(tb + o_cum) + T)) return rc;
     if (int rc = exclusive_scan(c, A.c_big, T, (u64*)(tb + o_cumb), (u64*)(tb + o_cumb) + T)) return rc;
-    u64 nz2[2] = {0, 0};
-    HIPC(hipMemcpyAsync(&nz2[0], (u64*)(tb + o_cum) + T, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipMemcpyAsync(&nz2[1], (u64*)(tb + o_cumb) + T, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(&nz_pin[0], (u64*)(tb + o_cum) + T, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(&nz_pin[1], (u64*)(tb + o_cumb) + T, 8, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
+    const u64 nz2[2] = {nz_pin[0], nz_pin[1]};
+    cst = *cst_pin;
     NZ = nz2[0] + nz2[1];
     if (comp_out) *comp_out = cst;
     if (NZ == 0) return 1;
@@ -2076,8 +2197,10 @@ int em_local_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids,
     P->n_small = A.ng_small;
   } else {
     if (int rc = exclusive_scan(c, A.c_nnz, T, (u64*)(tb + o_cum), (u64*)(tb + o_cum) + T)) return rc;
-    HIPC(hipMemcpyAsync(&NZ, (u64*)(tb + o_cum) + T, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipMemcpyAsync(&nz_pin[0], (u64*)(tb + o_cum) + T, 8, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
+    NZ = nz_pin[0];
+    cst = *cst_pin;
     if (comp_out) *comp_out = cst;
     if (NZ == 0) return 1;
     ng = (u32)((NZ - 1) / A.target_nnz + 1);
@@ -2088,11 +2211,14 @@ int em_local_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids,
   HIPC(hipMemsetAsync(tb + o_gr, 0, t1.off - o_gr, c->stream));
   A.g_rows = (u32*)(tb + o_gr); A.g_tr = (u32*)(tb + o_gt); A.g_nnz = (u32*)(tb + o_gn); A.row_fill = (u32*)(tb + o_rf); A.tr_fill = (u32*)(tb + o_tf);
   hipLaunchKernelGGL(k_eml_step<2>, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, A, T);
-  std::vector<u32> g_rows(ng), g_tr(ng), g_nnz(ng);
-  HIPC(hipMemcpyAsync(g_rows.data(), A.g_rows, ng * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(g_tr.data(), A.g_tr, ng * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(g_nnz.data(), A.g_nnz, ng * 4, hipMemcpyDeviceToHost, c->stream));
+  // the three size arrays are neighbours in the carve-up: one copy brings them (and the padding between them) to the host
+  const size_t g_span = (o_gn - o_gr) + (size_t)ng * 4;
+  if (int rc = plan_pin_ensure(c, g_span)) return rc;
+  HIPC(hipMemcpyAsync(c->plan_pin, tb + o_gr, g_span, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
+  const u32* const g_rows = (const u32*)c->plan_pin;
+  const u32* const g_tr = (const u32*)((const char*)c->plan_pin + (o_gt - o_gr));
+  const u32* const g_nnz = (const u32*)((const char*)c->plan_pin + (o_gn - o_gr));
   P->n_groups = ng; P->T = T; P->max_group_bytes = 0;
   P->row_base.assign(ng + 1, 0); P->tr_base.assign(ng + 1, 0); P->nz_base.assign(ng + 1, 0);
   for (u32 g = 0; g < ng; g++) {
@@ -3259,8 +3385,9 @@ int em_sell_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, 
   const u64 nseg = std::max(R, M);
   hipLaunchKernelGGL(k_sell_lens, dim3(grid_for(nseg, BLOCK)), dim3(BLOCK), 0, c->stream, B);
   hipLaunchKernelGGL(k_sell_sizes, dim3(grid_for(2 * (u64)ng, SELL_BUILD_WAVES)), dim3(64 * SELL_BUILD_WAVES), 0, c->stream, B);
-  std::vector<u32> gsz((size_t)ng * 4);
-  HIPC(hipMemcpyAsync(gsz.data(), B.gsz, (size_t)ng * 16, hipMemcpyDeviceToHost, c->stream));
+  if (int rc = plan_pin_ensure(c, (size_t)ng * 16)) return rc;
+  const u32* const gsz = (const u32*)c->plan_pin;
+  HIPC(hipMemcpyAsync(c->plan_pin, B.gsz, (size_t)ng * 16, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   P->n_groups = ng; P->n_small = C.n_small; P->T = T; P->row_base = C.row_base; P->tr_base = C.tr_base; P->single_all = C.single_all;
   P->rslice_base.assign(ng + 1, 0); P->cslice_base.assign(ng + 1, 0); P->rell_base.assign(ng + 1, 0); P->cell_base.assign(ng + 1, 0);
@@ -3280,7 +3407,7 @@ int em_sell_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, 
   const u64 nrs = P->rslice_base[ng], ncs = P->cslice_base[ng], nru = P->rell_base[ng], ncu = P->cell_base[ng];
   Carver pv;
   const size_t p_rsb = pv.take((ng + 1) * 4), p_csb = pv.take((ng + 1) * 4), p_reb = pv.take((ng + 1) * 8), p_ceb = pv.take((ng + 1) * 8);
-  const size_t p_rd = pv.take(nrs * 8 + 8), p_cdesc = pv.take(ncs * 8 + 8), p_re = pv.take(nru * 2 + 8), p_ce = pv.take(ncu * 2 + 8);
+  const size_t p_rd = pv.take(nrs * 8 + 8), p_cdesc = pv.take(ncs * 8 + 8), p_re = pv.take(nru * 2 + 16), p_ce = pv.take(ncu * 2 + 16);   // (16: ems_ld)
   const size_t p_cw = pv.take(R * 8 + 8), p_sg = pv.take(M * 8 + 8), p_ef = pv.take(M * 8 + 8), p_id = pv.take(M * 4 + 8);
   if (int rc = c->ems_plan.ensure(pv.off, 0, c->stream)) return rc;
   char* pb = (char*)c->ems_plan.p;
@@ -3303,17 +3430,18 @@ int em_sell_setup_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, 
   // the group bases live in the CSR plan's arena (pm_a), which other EM forms reuse: copy them next to the plan
   Carver bv;
   const size_t b_rb = bv.take((ng + 1) * 4), b_tb = bv.take((ng + 1) * 4), b_rf = bv.take(n_ecs * 4 + 8), b_ms = bv.take(T * 4 + 8), b_sa = bv.take(T * 8 + 8),
-               b_ef = bv.take(T * 8 + 8);
+               b_ef = bv.take(T * 8 + 8), b_gr = bv.take((size_t)ng * EMS_GREC_WORDS * 4 + 16);
   if (int rc = c->ems_maps.ensure(bv.off, 0, c->stream)) return rc;
   char* mb = (char*)c->ems_maps.p;
   HIPC(hipMemcpyAsync(mb + b_rb, cd.row_base, (ng + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
   HIPC(hipMemcpyAsync(mb + b_tb, cd.tr_base, (ng + 1) * 4, hipMemcpyDeviceToDevice, c->stream));
   hipLaunchKernelGGL(k_sell_maps, dim3(grid_for(std::max<u64>(n_ecs, T), BLOCK)), dim3(BLOCK), 0, c->stream, A, B, (u32*)(mb + b_rf), (u32*)(mb + b_ms));
   HIPC(hipMemcpyAsync(mb + b_sa, A.single_all, T * 8, hipMemcpyDeviceToDevice, c->stream));
+  *dev = EmSellDev{(const u32*)(mb + b_rb), (const u32*)(mb + b_tb), B.rslice_base, B.cslice_base, B.rell_base, B.cell_base, B.rdesc, B.cdesc, B.rell, B.cell,
+                   B.cw_new, B.single_new, B.eff_new, (const u32*)(mb + b_gr)};
+  hipLaunchKernelGGL(k_sell_group_rec, dim3(grid_for(ng, BLOCK)), dim3(BLOCK), 0, c->stream, *dev, ng, (u32*)(mb + b_gr));
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(c->stream));
-  *dev = EmSellDev{(const u32*)(mb + b_rb), (const u32*)(mb + b_tb), B.rslice_base, B.cslice_base, B.rell_base, B.cell_base, B.rdesc, B.cdesc, B.rell, B.cell,
-                   B.cw_new, B.single_new, B.eff_new};
   if (cache) { cache->row_final = (u32*)(mb + b_rf); cache->mslot = (u32*)(mb + b_ms); cache->single_all = (double*)(mb + b_sa); cache->d_eff = (double*)(mb + b_ef); }
   return 0;
 }

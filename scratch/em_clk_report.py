@@ -1,6 +1,6 @@
 """Reads the phase clocks k_em_sell<true> wrote (KAMD_EM_CLK=<file>): per wavefront of every group, one round of the first chunk.
 words: 0 round start, 1 rows pass done, 2 behind barrier 1, 3 columns pass done, 4 behind barrier 2, 5 nrs | ncs << 16, 6 nru | ncu << 32,
-7 wall clock (100 MHz) ticks of the round."""
+7 wall clock (100 MHz) ticks of the round; 16 kernel entry, 17 the group's tables in LDS, 18 start of round 0, 19 wall clock ticks from entry to round 0."""
 import sys
 import numpy as np
 
@@ -45,3 +45,10 @@ if words >= 16:
             if sel.any():
                 print(f"  width {lo:2d}-{hi:2d}: n {sel.sum():6d}  sums {t_sum[sel].mean():8.1f} clk ({(t_sum[sel] / np.maximum(width[sel], 1)).mean():6.1f} / trip)  scan+finish {t_fin[sel].mean():8.1f}"
                       f"  (split {t_fin[sel & (meta == 1)].mean() if (sel & (meta == 1)).any() else 0:8.1f}, plain {t_fin[sel & (meta == 0)].mean() if (sel & (meta == 0)).any() else 0:8.1f})")
+if words >= 20:
+    # what a launch costs a workgroup before its first round (lane 0 of every wavefront)
+    print("entry -> tables in LDS    ", q((c[:, :, 17] - c[:, :, 16]).max(1)))
+    print("tables in LDS -> round 0  ", q((c[:, :, 18] - c[:, :, 17]).max(1)))
+    print("entry -> round 0, clocks  ", q((c[:, :, 18] - c[:, :, 16]).max(1)))
+    print("entry -> round 0, wall ticks (10 ns)", q(c[:, :, 19].max(1)))
+    print("round / (entry -> round 0)", f"{(tot / np.maximum((c[:, :, 18] - c[:, :, 16]).max(1), 1)).mean():.3f}")

@@ -22,6 +22,7 @@
  *       BUSProcessor::processBuffer, a record's class and `-n` number  src/ProcessReads.cpp:1747-1749 -> kamd_read_ecs (a second pass after kamd_ec_finalize)
  *       BUSProcessor::processBuffer, barcode / UMI / sequence of a technology  src/ProcessReads.cpp:1486-1627, 1739-1746 -> kamd_bus_split, kamd_bus_records
  *       (the technology table and ParseTechnology, src/main.cpp:1283-1408, 778-870 -> kamd_bus_layout_parse)
+ *       `bustools sort | bustools count` between those records and quant-tcc (not part of the reference) -> kamd_bus_sort, kamd_bus_count
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -122,7 +123,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 9
+#define KAMD_ABI_VERSION 10
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -544,6 +545,41 @@ int kamd_bus_split(kamd_ctx*, const kamd_bus_layout*, const uint32_t* d_words, c
  * at most n.  A KAMD_READ_EC_FOREIGN row anywhere is an error (-4, with a text) and *n_out = 0: the batch was not part of the finalized result.
  * Same scratch, stream and guarantees as kamd_bus_split. */
 int kamd_bus_records(kamd_ctx*, const kamd_bus_tag* d_tags, const int32_t* d_ec, uint64_t n, kamd_bus_record* d_out, uint64_t* n_out);
+
+/* ---- BUS records -> a cells x classes matrix: what `bustools sort | bustools count` do, on the device ----
+ * The step between kamd_bus_records and the input of quant-tcc.  The rules (kamd_bussort.h restates them):
+ *   - key: barcode, umi, ec (signed), flags, most significant first -- the order of np.lexsort((flags, ec, umi, barcode)); 24 bytes, 24 digits of
+ *     8 bits.  `count` and `pad` are no part of it.
+ *   - collapse: records equal in all four key fields become one; count = the sum, held in 64 bits; pad = the first record's.
+ *   - rows: the distinct barcodes, ascending.  A group is a run of equal (barcode, umi), flags ignored.  A group of one class adds 1 to
+ *     (row, class); a group of several classes adds nothing on the device and is handed to the caller (bustools intersects the classes'
+ *     transcript sets; kallisto_amd/bus_sc.py does).
+ * kamd_bus_sort: d_rec[0 .. n) (device, 16-byte aligned, fewer than 2^32 - 1 records; n == 0 is fine) is sorted by key, stably; with `collapse` equal
+ * records are merged.  The result is left in d_rec[0 .. *n_out) (*n_out: host).  With d_ec_map every record's ec is replaced by d_ec_map[ec] before
+ * anything else; an ec outside [0, n_map) is an error (-4, the text gives their number) and d_rec is not written.  A collapsed count above
+ * 0xFFFFFFFF is an error (-4); d_rec is then unspecified.  An LSD radix sort with one pass per key byte in which two keys differ (a pre-pass
+ * reduces OR and AND of the keys): three launches per pass on the context stream, then flag / scan / scatter for the collapse.  The context stream
+ * is synchronised twice: once for the plan (and the map's range check), once for the output size.  The output is the same bytes on every run.
+ * Scratch, kept in the context: a second buffer of n records, 1 KiB of histogram per 1024 records, 8 bytes per record for the sums.
+ * out (nullable): passes = key bytes sorted by, key_bits = bits in which two keys differ, last_ms = the call by HIP events.
+ * Touches neither the EC state, the counts, the tuple table nor the fragment-length sample.
+ *
+ * kamd_bus_count: d_sorted[0 .. n) in key order (as kamd_bus_sort leaves it, collapsed or not; an adjacent pair out of order is an error, -4 with
+ * their number) -> d_barcodes[0 .. n_barcodes): the rows; d_entries[0 .. n_entries): the matrix, sorted by (row, ec) and unique;
+ * d_multi[0 .. n_multi_records): the records of the multi-class groups in input order, pad = their row.  All three are device buffers of n elements.
+ * KAMD_BUS_COUNT_UMIS: value = groups of that single class; KAMD_BUS_COUNT_READS: value = sum of the records' counts, UMIs ignored, no multi
+ * groups (bulk, layouts without a UMI).  A value above 0xFFFFFFFF is an error (-4).  Counted groups become unit records that go through
+ * kamd_bus_sort's passes and collapse a second time (entries of one (row, class) from different UMIs are not adjacent in the input); three
+ * synchronisations of the context stream in all.  n_umis: all groups, the multi-class ones included.  Same guarantees as kamd_bus_sort. */
+#define KAMD_BUS_COUNT_UMIS  0
+#define KAMD_BUS_COUNT_READS 1
+typedef struct { uint64_t n_in, n_out; uint32_t passes, key_bits; float last_ms; } kamd_bus_sort_stats;
+typedef struct { uint32_t row; int32_t ec; uint32_t value; } kamd_bus_entry;
+typedef struct { uint64_t n_records, n_barcodes, n_entries, n_umis, n_multi_groups, n_multi_records; float last_ms; } kamd_bus_count_stats;
+int kamd_bus_sort(kamd_ctx*, kamd_bus_record* d_rec /* in/out, [n] */, uint64_t n, const int32_t* d_ec_map /* nullable, [n_map] */, uint64_t n_map,
+                  int collapse, uint64_t* n_out /* host */, kamd_bus_sort_stats* out /* nullable */);
+int kamd_bus_count(kamd_ctx*, const kamd_bus_record* d_sorted, uint64_t n, int mode, uint64_t* d_barcodes /* [n] */, kamd_bus_entry* d_entries /* [n] */,
+                   kamd_bus_record* d_multi /* [n] */, kamd_bus_count_stats* out /* nullable */);
 
 /* ---- S3: EM ---- */
 /* Runs EMAlgorithm(counts, ...).run(n_iter, min_rounds) (src/EMAlgorithm.h:26-48,95-223) on the finalized EC result

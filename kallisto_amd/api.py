@@ -63,7 +63,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 9   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 10   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -98,6 +98,8 @@ READ_EC_FOREIGN = -2   # KAMD_READ_EC_FOREIGN: the item has a set that the conte
 BUS_MAX_PARTS = 8   # KAMD_BUS_MAX_PARTS
 BUS_TAG_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("flags", "<u4"), ("bc_len", "<u2"), ("umi_len", "<u2")])            # kamd_bus_tag
 BUS_RECORD_DTYPE = np.dtype([("barcode", "<u8"), ("umi", "<u8"), ("ec", "<i4"), ("count", "<u4"), ("flags", "<u4"), ("pad", "<u4")])   # kamd_bus_record = BUSData
+BUS_ENTRY_DTYPE = np.dtype([("row", "<u4"), ("ec", "<i4"), ("value", "<u4")])   # kamd_bus_entry
+BUS_COUNT_UMIS, BUS_COUNT_READS = 0, 1   # KAMD_BUS_COUNT_*
 
 
 class BusSubstr(C.Structure):
@@ -143,6 +145,17 @@ class _BusSplitStats(C.Structure):
     """kamd_bus_split_stats"""
     _fields_ = [("n_items", C.c_uint64), ("n_valid", C.c_uint64), ("n_dropped_umi", C.c_uint64), ("n_dropped_bc", C.c_uint64),
                 ("bc_len_hist", C.c_uint64 * 33), ("umi_len_hist", C.c_uint64 * 33), ("max_seq_len", C.c_int32), ("last_ms", C.c_float)]
+
+
+class _BusSortStats(C.Structure):
+    """kamd_bus_sort_stats"""
+    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("passes", C.c_uint32), ("key_bits", C.c_uint32), ("last_ms", C.c_float)]
+
+
+class _BusCountStats(C.Structure):
+    """kamd_bus_count_stats"""
+    _fields_ = [("n_records", C.c_uint64), ("n_barcodes", C.c_uint64), ("n_entries", C.c_uint64), ("n_umis", C.c_uint64), ("n_multi_groups", C.c_uint64),
+                ("n_multi_records", C.c_uint64), ("last_ms", C.c_float)]
 
 
 class BgzfMember(C.Structure):
@@ -254,6 +267,8 @@ _SYMBOLS = {
     "kamd_bus_split": (C.c_int, [C.c_void_p, C.POINTER(BusLayout), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_int32, C.POINTER(_BusSplitStats)]),
     "kamd_bus_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "kamd_bus_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(_BusSortStats)]),
+    "kamd_bus_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_BusCountStats)]),
     "kamd_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "kamd_em_run_partitioned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
@@ -335,6 +350,11 @@ def bus_tags_numpy(tags) -> np.ndarray:
 def bus_records_numpy(records) -> np.ndarray:
     """the int64 [n, 4] tensor of Context.bus_records -> a host array of BUS_RECORD_DTYPE (the 32-byte records of a BUS file)"""
     return np.ascontiguousarray(records.cpu().numpy()).reshape(-1).view(BUS_RECORD_DTYPE)
+
+
+def bus_entries_numpy(entries) -> np.ndarray:
+    """the int32 [n, 3] tensor of Context.bus_count -> a host array of BUS_ENTRY_DTYPE"""
+    return np.ascontiguousarray(entries.cpu().numpy()).reshape(-1).view(BUS_ENTRY_DTYPE)
 
 
 def packed_record_words(max_len: int) -> int:
@@ -644,6 +664,39 @@ class Context:
         n_out = C.c_uint64(0)
         _check(load_library().kamd_bus_records(self._h, tags.data_ptr(), d_ec.data_ptr(), int(n), out.data_ptr(), C.byref(n_out)), "kamd_bus_records")
         return out[:int(n_out.value)]
+
+    # ---- BUS records -> cells x classes (bustools sort | bustools count) ----
+    def bus_sort(self, records, ec_map=None, collapse: bool = True):
+        """kamd_bus_sort: the int64 device tensor [n, 4] of BUS records (Context.bus_records) is sorted IN PLACE by (barcode, umi, ec, flags), stably;
+        with `collapse` equal records are merged, counts summed.  ec_map (int32 device tensor, optional): every ec is replaced by ec_map[ec] first; an
+        ec outside the map raises and leaves `records` as it was.  Returns (records[:n_out], stats dict)."""
+        n = int(records.shape[0])
+        if n and not records.is_contiguous():
+            raise KallistoAmdError("bus_sort: the records must be a contiguous int64 [n, 4] tensor")
+        n_out, st = C.c_uint64(0), _BusSortStats()
+        _check(load_library().kamd_bus_sort(self._h, records.data_ptr() if n else None, n, ec_map.data_ptr() if ec_map is not None else None,
+                                            int(ec_map.numel()) if ec_map is not None else 0, 1 if collapse else 0, C.byref(n_out), C.byref(st)), "kamd_bus_sort")
+        return records[:int(n_out.value)], {"n_in": int(st.n_in), "n_out": int(st.n_out), "passes": int(st.passes), "key_bits": int(st.key_bits), "ms": float(st.last_ms)}
+
+    def bus_count(self, sorted_records, mode: int) -> dict:
+        """kamd_bus_count: records in key order (Context.bus_sort) -> barcodes (int64 [n_barcodes]: the rows, the barcodes' bits), entries (int32
+        [n_entries, 3]: kamd_bus_entry, see bus_entries_numpy; sorted by (row, ec), unique), multi (int64 [n_multi_records, 4]: the records of the
+        multi-class groups in input order, pad = row) and stats.  mode: BUS_COUNT_UMIS or BUS_COUNT_READS.  Unsorted input raises."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        n = int(sorted_records.shape[0])
+        if n and not sorted_records.is_contiguous():
+            raise KallistoAmdError("bus_count: the records must be a contiguous int64 [n, 4] tensor")
+        m = max(n, 1)
+        barcodes = torch.empty(m, dtype=torch.int64, device=dev)
+        entries = torch.empty((m, 3), dtype=torch.int32, device=dev)
+        multi = torch.empty((m, 4), dtype=torch.int64, device=dev)
+        st = _BusCountStats()
+        _check(load_library().kamd_bus_count(self._h, sorted_records.data_ptr() if n else None, n, int(mode), barcodes.data_ptr(), entries.data_ptr(),
+                                             multi.data_ptr(), C.byref(st)), "kamd_bus_count")
+        stats = {"n_records": int(st.n_records), "n_barcodes": int(st.n_barcodes), "n_entries": int(st.n_entries), "n_umis": int(st.n_umis),
+                 "n_multi_groups": int(st.n_multi_groups), "n_multi_records": int(st.n_multi_records), "ms": float(st.last_ms)}
+        return {"barcodes": barcodes[:stats["n_barcodes"]], "entries": entries[:stats["n_entries"]], "multi": multi[:stats["n_multi_records"]], "stats": stats}
 
     # ---- translated search (bus --aa) ----
     def cfc_frames(self, words, lens, n_reads: int, max_len: int):

@@ -1,18 +1,27 @@
 """`kallisto bus -x <technology>` over the library: a small Python driver that writes a `kallisto bus` output directory for a barcode / UMI technology.
 
-    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] files...
+    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] [--count] files...
 
 TECH is a technology name (10XV3, SURECELL, INDROPSV2, VASA-SEQ, ...) or a custom "bc:umi:seq" string (BusLayout.parse); the files come in sets of the
 technology's file count, plain or gzip.  Per batch of UNIT_RECORDS read sets the driver runs
 
-    reset -> bus_split -> pseudoalign -> finalize -> read_ecs -> bus_records -> download of the records and of the batch's classes
+    reset -> bus_split -> pseudoalign -> finalize -> read_ecs -> bus_records -> bus_sort (the batch's classes as its map) -> download of the batch's classes
 
-Class ids are batch-local; they are mapped to the ids of matrix.ec by transcript set, in order of first appearance, so the input is read once and
-nothing of a batch is kept but its records.  output.bus holds the records sorted by barcode, UMI, class and flags and collapsed with summed counts
+Class ids are batch-local; they are mapped to the ids of matrix.ec by transcript set, batch by batch in order of first appearance (the new sets of a batch in ascending order), so the input is read once and
+nothing of a batch is kept but its records.  The records stay on the device: every batch's are sorted and collapsed there (kamd_bus_sort), the
+sorted chunks are merged by sorting their concatenation whenever more than merge_records records have come in since the last merge, and only the
+run's final records are downloaded.  output.bus holds them sorted by barcode, UMI, class and flags and collapsed with summed counts
 (--bus-per-read: one record per read); its header lengths are the layout's fixed sums or the modes of the run's length histograms.  run_info.json:
 n_reads = read sets read, n_processed = those that survive the drop rules (a part of barcode or UMI outside its read), n_pseudoaligned, n_unique.
 
-This is a driver for moderate inputs: records of the whole run are held in host memory and the FASTQ text is read through Python.  It is not the
+--count: what `bustools count` makes of output.bus, into out/counts/: output.mtx (MatrixMarket coordinate integer, rows = barcodes, columns =
+classes, 1-based, sorted by row then column), output.barcodes.txt (the rows' barcodes as bases), output.ec.txt (the classes: matrix.ec).  The matrix
+is counted on the device (kamd_bus_count: distinct UMIs per (barcode, class), or reads where the layout has no UMI); a UMI whose records name
+several classes is resolved here as bustools does: the transcript sets of its classes are intersected, an empty intersection drops the UMI,
+otherwise it counts 1 for the class of the intersection, which is appended to matrix.ec when it is new.  `kallisto_amd_quant quant-tcc -e
+counts/output.ec.txt counts/output.mtx` takes the result.
+
+This is a driver for moderate inputs: the collapsed records of the whole run are held in device memory and the FASTQ text is read through Python.  It is not the
 streaming C++ front-end (`kallisto_amd_quant bus` takes `-x bulk` only): the product is the C ABI, which a front-end that parses `-x` itself binds.
 """
 from __future__ import annotations
@@ -29,6 +38,7 @@ import numpy as np
 from . import api as A
 
 UNIT_RECORDS = 1 << 20   # read sets per batch
+MERGE_RECORDS = 1 << 25  # records that come in between two merges of the sorted chunks
 
 
 def _open(path):
@@ -71,7 +81,8 @@ def _pack_unit(ctx, texts, n_records, n_files):
     return words, lens, n_records, max_len
 
 
-def run(technology, index_path, out_dir, files, strand=None, no_jump=False, union=False, per_read=False, unit_records=UNIT_RECORDS, device=0, call=""):
+def run(technology, index_path, out_dir, files, strand=None, no_jump=False, union=False, per_read=False, unit_records=UNIT_RECORDS, device=0, call="", count=False,
+        merge_records=MERGE_RECORDS):
     layout, default_strand = A.BusLayout.parse(technology)
     if strand is None:
         strand = default_strand
@@ -83,7 +94,14 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
     ctx.upload(index)
     opts = A.QuantOpts(0, 200.0, 20.0, 1, strand, 1 if no_jump else 0, 1 if union else 0)   # what `bus` runs single-end reads with
     ec_of, ec_sets = {}, []          # transcript set -> id of matrix.ec, in order of first appearance
-    chunks = []                      # the records of every batch, classes already global
+    chunks, since_merge = [], 0      # sorted device chunks of records, classes already global; records that came in since the last merge
+    torch = ctx.torch
+
+    def merge():
+        """the chunks held -> one sorted (and, unless per_read, collapsed) chunk"""
+        if len(chunks) > 1:
+            both, _ = ctx.bus_sort(torch.cat(chunks), None, collapse=not per_read)
+            chunks[:] = [both.clone()]   # (the copy lets go of the records the collapse left behind)
     bc_hist, umi_hist = np.zeros(33, np.uint64), np.zeros(33, np.uint64)
     n_reads = n_processed = n_pseudoaligned = n_unique = 0
     for s in range(0, len(files), layout.n_files):
@@ -107,37 +125,36 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
                 ctx.pseudoalign(opts, sp["seq_words"], sp["seq_len"], nv, sp["seq_max_len"])
                 ecs = ctx.finalize()
                 d_ec, _ = ctx.read_ecs(opts, sp["seq_words"], sp["seq_len"], nv, sp["seq_max_len"])
-                rec = A.bus_records_numpy(ctx.bus_records(sp["tags"], d_ec, nv)).copy()
-                # batch-local rows -> ids of matrix.ec
+                d_rec = ctx.bus_records(sp["tags"], d_ec, nv)
+                # batch-local rows -> ids of matrix.ec.  The rows of a finalized result come in no fixed order, so the sets a batch brings in
+                # are numbered in ascending order of their transcripts: two runs over the same input write the same bytes
                 row_to_ec = np.zeros(max(len(ecs.counts), 1), np.int32)
-                for r in range(len(ecs.counts)):
-                    key = tuple(ecs.ec_ids[int(ecs.ec_off[r]):int(ecs.ec_off[r + 1])].tolist())
-                    e = ec_of.get(key)
-                    if e is None:
-                        e = ec_of[key] = len(ec_sets)
-                        ec_sets.append(key)
-                    row_to_ec[r] = e
+                keys = [tuple(ecs.ec_ids[int(ecs.ec_off[r]):int(ecs.ec_off[r + 1])].tolist()) for r in range(len(ecs.counts))]
+                for key in sorted(k for k in keys if k not in ec_of):
+                    ec_of[key] = len(ec_sets)
+                    ec_sets.append(key)
+                for r, key in enumerate(keys):
+                    row_to_ec[r] = ec_of[key]
                     if len(key) == 1:
                         n_unique += int(ecs.counts[r])
-                rec["ec"] = row_to_ec[rec["ec"]]
-                n_pseudoaligned += len(rec)
-                chunks.append(rec)
+                n_pseudoaligned += int(d_rec.shape[0])
+                if d_rec.shape[0] == 0:
+                    continue
+                srt, _ = ctx.bus_sort(d_rec, torch.from_numpy(row_to_ec).to(d_rec.device), collapse=not per_read)
+                chunks.append(srt.clone())
+                since_merge += int(d_rec.shape[0])
+                if since_merge > merge_records:
+                    merge()
+                    since_merge = 0
         finally:
             for h in handles:
                 h.close()
-    rec = np.concatenate(chunks) if chunks else np.zeros(0, A.BUS_RECORD_DTYPE)
-    order = np.lexsort((rec["flags"], rec["ec"], rec["umi"], rec["barcode"]))
-    rec = rec[order]
-    if not per_read and len(rec):   # collapse equal (barcode, UMI, class, flags), counts summed
-        first = np.ones(len(rec), bool)
-        first[1:] = (rec["barcode"][1:] != rec["barcode"][:-1]) | (rec["umi"][1:] != rec["umi"][:-1]) | (rec["ec"][1:] != rec["ec"][:-1]) | (rec["flags"][1:] != rec["flags"][:-1])
-        starts = np.flatnonzero(first)
-        runs = np.diff(np.append(starts, len(rec)))
-        assert runs.max() <= 0xFFFFFFFF   # (`count` is 32 bits; a run that long is beyond this driver)
-        rec = rec[starts].copy()
-        rec["count"] = runs
+    merge()
+    d_all = chunks[0] if chunks else torch.zeros((0, 4), dtype=torch.int64, device=f"cuda:{device}")
+    rec = A.bus_records_numpy(d_all)
     bclen, umilen = layout.header_lens(bc_hist, umi_hist)
     os.makedirs(out_dir, exist_ok=True)
+    counted = _count(ctx, d_all, layout, ec_of, ec_sets, bclen, os.path.join(out_dir, "counts")) if count else {}
     text = b"BUS file produced by kallisto"
     with open(os.path.join(out_dir, "output.bus"), "wb") as f:
         f.write(b"BUS\0" + np.array([1, bclen, umilen, len(text)], "<u4").tobytes() + text)
@@ -155,7 +172,60 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
     with open(os.path.join(out_dir, "run_info.json"), "w") as f:
         json.dump(info, f, indent=1)
         f.write("\n")
+    info = dict(info, **counted)   # (run_info.json keeps the reference's keys)
     return info
+
+
+def count_mode(layout):
+    """distinct UMIs per (barcode, class), or reads where the layout has no UMI"""
+    return A.BUS_COUNT_READS if layout.parts("umi")[0][0] < 0 else A.BUS_COUNT_UMIS
+
+
+def resolve_multi(multi, matrix, ec_of, ec_sets):
+    """the rule of `bustools count` for a UMI whose records name several classes, restated: multi = the host copy of Context.bus_count's multi records,
+    matrix = {(row, class): value} of its entries.  Per group the transcript sets of its classes are intersected; an empty intersection drops the
+    group, otherwise it adds 1 to (row, class of the intersection), a new class being appended to ec_sets / ec_of.  Returns the groups dropped."""
+    groups = {}   # (row, UMI) -> classes: d_multi holds whole groups, each with its barcode's row in pad
+    for row, umi, e in zip(multi["pad"].tolist(), multi["umi"].tolist(), multi["ec"].tolist()):
+        groups.setdefault((row, umi), []).append(e)
+    dropped = 0
+    for (row, _), classes in groups.items():
+        common = set(ec_sets[classes[0]])
+        for e in classes[1:]:
+            common &= set(ec_sets[e])
+        if not common:
+            dropped += 1
+            continue
+        key = tuple(sorted(common))
+        e = ec_of.get(key)
+        if e is None:
+            e = ec_of[key] = len(ec_sets)
+            ec_sets.append(key)
+        matrix[(row, e)] = matrix.get((row, e), 0) + 1
+    return dropped
+
+
+def _count(ctx, d_rec, layout, ec_of, ec_sets, bclen, out_dir):
+    """the run's sorted records -> out_dir/output.mtx, output.barcodes.txt, output.ec.txt (ec_sets grows by the classes the multi-class UMIs resolve to)"""
+    c = ctx.bus_count(d_rec, count_mode(layout))
+    ent = A.bus_entries_numpy(c["entries"])
+    matrix = dict(zip(zip(ent["row"].tolist(), ent["ec"].tolist()), ent["value"].tolist()))
+    resolve_multi(A.bus_records_numpy(c["multi"]), matrix, ec_of, ec_sets)
+    barcodes = c["barcodes"].cpu().numpy().view(np.uint64)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "output.mtx"), "w") as f:
+        f.write("%%MatrixMarket matrix coordinate integer general\n")
+        f.write("%d\t%d\t%d\n" % (len(barcodes), len(ec_sets), len(matrix)))
+        for (row, e), v in sorted(matrix.items()):
+            f.write("%d\t%d\t%d\n" % (row + 1, e + 1, v))
+    with open(os.path.join(out_dir, "output.barcodes.txt"), "w") as f:
+        for b in barcodes.tolist():
+            f.write("".join("ACGT"[(b >> (2 * (bclen - 1 - i))) & 3] for i in range(bclen)) + "\n")
+    with open(os.path.join(out_dir, "output.ec.txt"), "w") as f:
+        for e, s in enumerate(ec_sets):
+            f.write("%d\t%s\n" % (e, ",".join(map(str, s))))
+    st = c["stats"]
+    return {"n_barcodes": st["n_barcodes"], "n_umis": st["n_umis"], "n_multi_umis": st["n_multi_groups"]}
 
 
 def main(argv=None):
@@ -170,11 +240,13 @@ def main(argv=None):
     ap.add_argument("--no-jump", action="store_true")
     ap.add_argument("--union", action="store_true")
     ap.add_argument("--bus-per-read", action="store_true")
+    ap.add_argument("--count", action="store_true", help="also write the barcodes x classes matrix of the records into <output-dir>/counts")
     ap.add_argument("--unit-records", type=int, default=UNIT_RECORDS, help=argparse.SUPPRESS)
+    ap.add_argument("--merge-records", type=int, default=MERGE_RECORDS, help=argparse.SUPPRESS)
     ap.add_argument("files", nargs="+")
     a = ap.parse_args(argv)
     try:
-        info = run(a.technology, a.index, a.output_dir, a.files, a.strand, a.no_jump, a.union, a.bus_per_read, a.unit_records,
+        info = run(a.technology, a.index, a.output_dir, a.files, a.strand, a.no_jump, a.union, a.bus_per_read, a.unit_records, count=a.count, merge_records=a.merge_records,
                    call="python -m kallisto_amd.bus_sc " + " ".join(sys.argv[1:] if argv is None else argv))
     except A.KallistoAmdError as e:
         print("Error:", e, file=sys.stderr)

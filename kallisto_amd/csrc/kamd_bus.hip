@@ -3,7 +3,7 @@
 //
 //   k_bus_count       one thread per input item: what the lengths of its reads decide (dropped or not, the fields' lengths, the cut's length) -> the
 //                     surviving items of the block, the drops, the two length histograms (LDS bins, one global add per non-empty bin and block)
-//   k_bus_scan        one block: exclusive scan of the block counts in place, 256 at a time with a running carry; the total is n_valid
+//   k_bus_scan        (kamd_bus_scan.h) one block: exclusive scan of the block counts in place, 256 at a time with a running carry; the total is n_valid
 //   k_bus_scatter     one thread per input item again: rank among the block's survivors by ballot -> compact position j; tag, source item, cut length
 //   k_bus_cut         BUS_CUT_LANES lanes per compact item: the cut sequence re-packed from base `start`, the lanes of an item writing consecutive words
 //                     (a wavefront writes 8 consecutive records); the cut's "has an N" flag is the OR of its mask words over the item's lanes
@@ -13,11 +13,11 @@
 // separate launches on the context stream: nothing waits for another workgroup inside a launch.  Scratch: one u32 per 256 items and the counters.
 #include "kamd_dev.h"
 #include "kamd_bustag.h"
+#include "kamd_bus_scan.h"
 
 namespace {
 
 constexpr int BUS_CUT_LANES = 8;
-constexpr int BUS_WAVES = BLOCK / 64;
 
 struct BusCounters {
   u64 n_valid, n_drop_umi, n_drop_bc, n_foreign;
@@ -30,17 +30,6 @@ __device__ __forceinline__ kamd::BusLens item_lens(const kamd_bus_layout& L, con
   *l0 = min((int)lens[i * L.n_files], max_len);
   *l1 = L.n_files > 1 ? min((int)lens[i * L.n_files + 1], max_len) : 0;
   return kamd::bus_item_lens(L, *l0, *l1);
-}
-
-// rank of a thread's item among the block's items with `valid`, in thread order
-__device__ __forceinline__ u32 block_rank(bool valid, u32* s_w) {
-  const u64 b = __ballot(valid);
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  if (lane == 0) s_w[wave] = (u32)__popcll(b);
-  __syncthreads();
-  u32 off = 0;
-  for (int w = 0; w < wave; w++) off += s_w[w];
-  return off + (u32)__popcll(b & ((1ULL << lane) - 1ULL));
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bus_count(kamd_bus_layout L, const uint16_t* __restrict__ lens, u64 n, int max_len, int seq_max_len, u32* __restrict__ blk_cnt,
@@ -73,30 +62,6 @@ __global__ __launch_bounds__(BLOCK) void k_bus_count(kamd_bus_layout L, const ui
     if (n_umi) atomicAdd(&ctr->n_drop_umi, (u64)n_umi);
     if (n_bc) atomicAdd(&ctr->n_drop_bc, (u64)n_bc);
   }
-}
-
-// blk[0 .. nb): counts -> exclusive offsets, in place; *total = their sum
-__global__ __launch_bounds__(BLOCK) void k_bus_scan(u32* __restrict__ blk, u64 nb, u64* total) {
-  __shared__ u32 s_w[BUS_WAVES];
-  __shared__ u32 s_carry;
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (u64 base = 0; base < nb; base += BLOCK) {   // (nb is uniform: every thread makes every trip)
-    const u64 i = base + threadIdx.x;
-    const u32 v = i < nb ? blk[i] : 0u;
-    const u32 incl = wave_incl_scan(v);
-    if (lane == 63) s_w[wave] = incl;
-    __syncthreads();
-    u32 woff = 0, tot = 0;
-    for (int w = 0; w < BUS_WAVES; w++) { if (w < wave) woff += s_w[w]; tot += s_w[w]; }
-    const u32 carry = s_carry;
-    if (i < nb) blk[i] = carry + woff + incl - v;
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry = carry + tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = s_carry;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_bus_scatter(kamd_bus_layout L, const u32* __restrict__ words, const uint16_t* __restrict__ lens, u64 n, int max_len,

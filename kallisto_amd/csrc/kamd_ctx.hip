@@ -195,7 +195,8 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
                   &c->em_segoff, &c->em_segt, &c->em_partial, &c->em_a0, &c->em_a1, &c->em_single, &c->em_actflag, &c->em_actpos, &c->em_active, &c->pt_label, &c->pt_flag, &c->pt_len,
                   &c->pt_rowpos, &c->pt_nnzpos, &c->pt_off, &c->pt_ids, &c->pt_counts, &c->pt_wcounts, &c->pt_hist, &c->pt_ck_alpha,
                   &c->pt_ck_a, &c->fq_tiles, &c->fq_nlpos[0], &c->fq_nlpos[1], &c->fq_recs, &c->fq_res, &c->fq_words, &c->fq_len, &c->aa_frames, &c->aa_flen, &c->aa_scratch, &c->aa_offlist, &c->aa_ctr, &c->inf_members, &c->inf_res, &c->txt_counts, &c->txt_res,
-                  &c->rec_table, &c->rec_scratch, &c->rec_big_scratch, &c->rec_big_items, &c->rec_ctr, &c->bus_blk, &c->bus_ctr})
+                  &c->rec_table, &c->rec_scratch, &c->rec_big_scratch, &c->rec_big_items, &c->rec_ctr, &c->bus_blk, &c->bus_ctr,
+                  &c->bsort_b, &c->bsort_hist, &c->bsort_tot, &c->bsort_sum, &c->bsort_ctr, &c->bcnt_units, &c->bcnt_gstart, &c->bcnt_mark, &c->bcnt_blk})
     b->release();
   delete c;
 }

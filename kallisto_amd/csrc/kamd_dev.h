@@ -13,6 +13,8 @@
 //                    table and look-up in kamd_readec.h
 //   kamd_bus.hip     barcode / UMI technologies: tags, drops and the cut sequence of every item, compacted (kamd_bus_split), and the 32-byte BUS records
 //                    of a cut batch (kamd_bus_records); per-item rules in kamd_bustag.h, the layout parser in kamd_bus.cpp
+//   kamd_bussort.hip BUS records -> cells x classes: the stable LSD sort with collapse (kamd_bus_sort) and rows / distinct UMIs per class / multi-class
+//                    groups (kamd_bus_count); per-record rules in kamd_bussort.h, the scan both bus units share in kamd_bus_scan.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -355,6 +357,9 @@ struct kamd_ctx {
   // barcode / UMI technologies (kamd_bus.hip): the survivors per block of 256 items (scanned in place), the counters of a call
   DBuf bus_blk, bus_ctr;
   hipEvent_t bus_ev[2] = {nullptr, nullptr};
+  // BUS records -> cells x classes (kamd_bussort.hip): the second buffer of the sort (n records), the [digit][block] histograms and their 256 totals,
+  // the 64-bit sums of the collapse, the counters of a call; kamd_bus_count's unit records (its second sort's input), group starts, per-record marks
+  DBuf bsort_b, bsort_hist, bsort_tot, bsort_sum, bsort_ctr, bcnt_units, bcnt_gstart, bcnt_mark, bcnt_blk;
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 

@@ -2,7 +2,9 @@
 // helpers, the growable device buffer, the context, and the host functions one unit calls in another.
 //   kamd_match.hip   kernel A (k_match_v3), k_classify, the straight-line matchers (overflow / explicit sets / fragment lengths), kamd_pseudoalign, kamd_fld_*
 //   kamd_ec.hip      exact de-duplication of records and tuples, EC resolution (k_resolve*), kamd_ec_*
-//   kamd_em.hip      the EM in all its forms (component-local k_em_sell, hybrid, streamed, CSR), bootstrap
+//   kamd_em.hip      the EM in its component-local (k_em_sell), hybrid and CSR forms, connected components and the partitioned run, bootstrap
+//   kamd_em_stream.hip  ... its streamed form (k_pm_*); the passes that form and the hybrid both instantiate in kamd_em_stream.h, what the two
+//                    EM units share in kamd_em_int.h
 //   kamd_io.hip      FASTQ text in HBM -> packed reads
 //   kamd_ctx.hip     context, index upload, tuning, diagnostics, communicators and what runs over them
 //   kamd_ixbuild.hip the k-mer table built on the device (upload of an index loaded with kamd_index_load_deferred), kamd_ctx_table_*

@@ -1,5 +1,6 @@
-// kamd_em.hip -- the EM (EMAlgorithm::run) in all its forms, connected components, bootstrap (Bootstrap::run_em, Multinomial::sample)
-#include "kamd_dev.h"
+// kamd_em.hip -- the EM (EMAlgorithm::run) in its CSR, component-local and hybrid forms, connected components, bootstrap (Bootstrap::run_em,
+// Multinomial::sample).  The streamed form is kamd_em_stream.hip; the passes it and the hybrid both instantiate: kamd_em_stream.h; the types: kamd_em_int.h
+#include "kamd_em_stream.h"
 
 namespace {
 
@@ -13,30 +14,6 @@ namespace {
 // alpha is double-buffered (round i reads A[i&1], writes A[(i+1)&1]); the clamp of the final round (:212-221) is applied
 // on read, so the unclamped buffer is alpha_before_zeroes_.
 // ------------------------------------------------------------------------------------------------------------------
-// Loop control without a control kernel.  Two records, indexed by the parity of the launch: the kernels of a round read
-// the record the PREVIOUS round left (iter, final flag, number of transcripts that still changed) and every block derives
-// from it -- identically -- what the reference's loop would do next (:202-221); block 0 of k_em_rows publishes that as this
-// round's record, k_em_final accumulates the round's change count into it.  Nothing is read and written in the same launch.
-struct EmState {
-  int iter;         // round index i this record's round ran as (-1: before the first round)
-  int chcount;      // transcripts with next > 1e-2 that moved by more than 1 % in that round (:177-179)
-  int final_round;  // finalRound: the round read the clamped alpha and was the last one
-  int done;
-  int rounds;       // i at exit ("ran for i rounds")
-  int force_final;  // host request (partitioned EM): the next round is the final round
-  int pad[2];
-};
-struct EmNow { int it, fin, done, rounds; };
-__host__ __device__ inline EmNow em_next_round(const EmState& prev, int n_iter, int min_rounds, bool spec) {
-  EmNow n; n.it = prev.iter; n.fin = prev.final_round; n.done = prev.done; n.rounds = prev.rounds;
-  if (n.done) return n;                                                              // (fin keeps telling how the loop ended)
-  if (prev.final_round) { n.done = 1; n.rounds = prev.iter; return n; }              // :207-209 (break: i is not incremented)
-  const bool stopEM = !spec && prev.chcount == 0 && prev.iter > min_rounds;          // :202-205
-  n.it = prev.iter + 1;
-  n.fin = (stopEM || prev.force_final) ? 1 : 0;                                      // :212-221 (clamp applied on read)
-  if (n.it >= n_iter) { n.done = 1; n.rounds = n_iter; }                             // the loop ran out
-  return n;
-}
 // Algebra used by the kernels.  With a_t = alpha_t / eff_len_t the reference's row pass
 //     denom_e = sum_t alpha_t * (wc_e / eff_t) = wc_e * S_e,  S_e = sum_t a_t          (:152-154, weights.cpp:236)
 // and its update  (w_et * alpha_t) * (count_e / denom_e) = a_t * g_e,  g_e = count_e / S_e   (:161-164; wc_e cancels,
@@ -215,538 +192,6 @@ __global__ __launch_bounds__(BLOCK) void k_em_final(const u64* __restrict__ seg_
   __syncthreads();
   if (threadIdx.x == 0 && blk_ch) atomicAdd(&st[parity].chcount, blk_ch);
 }
-// ------------------------------------------------------------------------------------------------------------------
-// Kernel B, streamed form: two launches per round (rows, columns) over a re-laid-out matrix.  At the sizes of a
-// transcriptome (a few 1e6 non-zeros) a round is bound by dependent-load latency and launch count, not by bytes: the CSR
-// form above chases row offsets -> ids -> a[] (three dependent latencies per kernel, three kernels).  Re-layout, once per run:
-//   * only rows with >= 2 transcripts and only transcripts that occur in such a row are kept ("m-space", compact ids);
-//     singleton rows are the constant single[] term of their transcript
-//   * both directions of the matrix are FLAGGED STREAMS: entry = index | PM_END on the last entry of a row (column).
-//     No offset arrays are read in the loop.  A wavefront owns one chunk of 64 x K consecutive entries (each lane K
-//     consecutive ones: K/4 16-byte loads, then K independent 8-byte gathers -- two dependent memory latencies per launch),
-//     reduces them with a lane-local pass + ONE segmented wavefront scan, stages the segment sums in LDS and finishes them
-//     lane-parallel (coalesced constants and stores, no divergent divisions)
-//   * a segment that crosses into a chunk from the left is re-read by that chunk if the part outside is short (<= 256
-//     entries, loads issued together with the chunk's own), else completed by a small fix-up launch from the chunks'
-//     left/right partial sums in chunk order (deterministic summation, no floating-point atomics); that launch only exists
-//     when such segments do
-// A persistent single-launch form with grid barriers was built and measured first (scratch/em_persistent_kernel_attempt):
-// one grid barrier costs 4.9-6.3 us on 256 CUs (kamd_debug_grid_barrier), a kernel boundary ~1.7 us, so launches win.
-// ------------------------------------------------------------------------------------------------------------------
-constexpr u32 PM_END = 0x80000000u;
-constexpr u32 PM_NONE = 0xFFFFFFFFu;
-constexpr u32 PM_HEAVY = 0x80000000u;
-constexpr u32 PM_LONG = 0x40000000u;      // head word: the crossing segment has more than 64 * PM_HEAD entries before the chunk, at most PM_LOOP_MAX: the chunk re-reads them in a loop
-constexpr u32 PM_LOOP_MAX = 32768;
-constexpr int PM_BLOCK = 256;         // 4 wavefronts = 4 chunks per block
-constexpr int PM_HEAD = 4;            // a crossing segment with <= 64 * PM_HEAD entries before the chunk is re-read by the chunk
-constexpr int PM_LDS_SLOTS = 512;     // segment sums staged per wavefront and window
-struct PmSide {
-  const u32* stream;     // [n_chunks * 64 * K] index | PM_END; the tail padding points at a sentinel whose value is 0; 64 * PM_HEAD
-                         // readable entries (any valid index) in front of it
-  const u32* seg_base;   // [n_chunks] segment that contains the chunk's first entry
-  const u32* head;       // [n_chunks] entries of that segment before the chunk: 0, 1..64*PM_HEAD (re-read), PM_HEAVY (partials)
-  const u32* fix_first;  // [n_chunks] heavy crossing segment that ENDS in this chunk: the chunk it started in, else PM_NONE
-  const u32* lane_word;  // [n_chunks * 64] per lane of the chunk: segment ends below the lane | ends in the lane << 12 | distance to the
-                         // nearest lane at or below it that holds an end (lane + 1: none) << 18 -- what the passes would otherwise
-                         // recount from the END flags every round
-  double* lp;            // [n_chunks] sum of the chunk's entries up to its first segment end (all of them if there is none)
-  double* rp;            // [n_chunks] sum of the entries after the chunk's last segment end
-  u32 n_chunks;
-};
-struct PmArgs {
-  PmSide rows, cols;
-  const u64* cw;           // [R] count | weight count << 32 of the kept rows
-  double* g;               // [R + 1]; g[R] = 0 is the sentinel the column stream's padding points at
-  double* alpha0; double* alpha1; double* a0; double* a1;   // [M + 1]; a*[M] = 0 is the row stream's sentinel
-  double* ac0; double* ac1;   // [M + 1] a with the final round's clamp (alpha < alpha_limit / 10 -> 0, EMAlgorithm.h:212-221): what the final round reads
-  const double* single; const double* eff;   // [M]
-  u32 R, M;
-  int n_iter, min_rounds;
-  EmState* st;             // the two parity-indexed loop-control records (see EmState)
-  int* spec_hist;          // partitioned EM: per-round change counts of this rank (the stop rule is applied by the host); else null
-};
-
-// Wavefront scans on the DPP data path (row_shr within the rows of 16 lanes, then row_bcast:15 / row_bcast:31 across
-// rows): six VALU steps instead of six LDS round trips (__shfl_up is ds_bpermute_b32, ~100+ cycles each, and the steps of
-// a scan depend on each other).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ u32 pm_dpp(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, true); }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double pm_dpp(double v) {
-  const u32 lo = pm_dpp<CTRL, ROW_MASK>((u32)__double2loint(v)), hi = pm_dpp<CTRL, ROW_MASK>((u32)__double2hiint(v));
-  return __hiloint2double((int)hi, (int)lo);
-}
-__device__ __forceinline__ u32 pm_scan_incl(u32 x) {   // inclusive prefix sum over the 64 lanes
-  x += pm_dpp<0x111, 0xF>(x); x += pm_dpp<0x112, 0xF>(x); x += pm_dpp<0x114, 0xF>(x); x += pm_dpp<0x118, 0xF>(x);
-  x += pm_dpp<0x142, 0xA>(x);   // row_bcast:15 into rows 1 and 3
-  x += pm_dpp<0x143, 0xC>(x);   // row_bcast:31 into rows 2 and 3
-  return x;
-}
-// segmented inclusive sum: lane l gets the sum over lanes (l - reach, l] where reach = distance to the nearest segment
-// start at or below l (0: the lane starts a segment itself; l + 1: none below)
-__device__ __forceinline__ double pm_scan_seg(double y, int reach, int lane) {
-  const int r = lane & 15;   // position inside the row
-  { const double t = pm_dpp<0x111, 0xF>(y); if (reach >= 1 && r >= 1) y += t; }
-  { const double t = pm_dpp<0x112, 0xF>(y); if (reach >= 2 && r >= 2) y += t; }
-  { const double t = pm_dpp<0x114, 0xF>(y); if (reach >= 4 && r >= 4) y += t; }
-  { const double t = pm_dpp<0x118, 0xF>(y); if (reach >= 8 && r >= 8) y += t; }
-  // rows 1 and 3 take the total of the row before them if their run reaches back past the row's first lane
-  { const double t = pm_dpp<0x142, 0xA>(y); if ((lane & 16) && reach > r) y += t; }
-  // rows 2 and 3 take lane 31's value if their run reaches back past lane 32
-  { const double t = pm_dpp<0x143, 0xC>(y); if (lane >= 32 && reach > lane - 32) y += t; }
-  return y;
-}
-__device__ __forceinline__ double pm_wave_sum(double x) {   // sum over the 64 lanes, in every lane
-  x += pm_dpp<0x111, 0xF>(x); x += pm_dpp<0x112, 0xF>(x); x += pm_dpp<0x114, 0xF>(x); x += pm_dpp<0x118, 0xF>(x);
-  x += pm_dpp<0x142, 0xA>(x); x += pm_dpp<0x143, 0xC>(x);
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 63), __builtin_amdgcn_readlane(__double2loint(x), 63));
-}
-// what is done with a finished segment sum: load() fetches the segment's constants (issued before the sums are known,
-// coalesced: consecutive lanes finish consecutive segments), finish() consumes them with the sum
-struct PmRowEmit {   // g_e = count_e / S_e; rows the reference skips get 0: count 0 (:133-135), denom below denorm_min (:156-158)
-  const u64* cw; double* g;
-  using Ctx = u64;
-  __device__ __forceinline__ Ctx load(u32 r) const { return cw[r]; }
-  __device__ __forceinline__ void finish(u32 r, const Ctx& w, double S) const {
-    const u32 cnt = (u32)w, wc = (u32)(w >> 32);
-    g[r] = (cnt == 0 || (double)wc * S < 4.9406564584124654e-324) ? 0.0 : (double)cnt / S;
-  }
-};
-struct PmColEmit {   // next_t = single_t + a_t * sum_e g_e and the convergence test of :176-199
-  const double* alpha_cur; const double* a_cur; const double* single; const double* eff;
-  double* alpha_nx; double* a_nx; double* ac_nx; int* ch; int clamp;   // a_cur is the clamped copy in the final round
-  struct Ctx { double al, at, sg, ef; };
-  __device__ __forceinline__ Ctx load(u32 m) const { return Ctx{alpha_cur[m], a_cur[m], single[m], eff[m]}; }
-  __device__ __forceinline__ void finish(u32 m, const Ctx& x, double acc) const {
-    const double al = (clamp && x.al < 1e-7 / 10.0) ? 0.0 : x.al;
-    const double nx = x.sg + x.at * acc;
-    if (nx > 1e-2 && (fabs(nx - al) / nx) > 1e-2) ++*ch;
-    const double an = nx / x.ef;
-    alpha_nx[m] = nx;
-    a_nx[m] = an;
-    ac_nx[m] = nx < 1e-7 / 10.0 ? 0.0 : an;
-  }
-};
-
-// one wavefront, one chunk: value of entry j = src[index_j]; every segment that ends in the chunk is finished here unless it
-// crossed in from far to the left (PM_HEAVY: pm_fix)
-// (in two steps so that the kernels can issue the chunk's loads BEFORE they use the round's loop-control record: both are
-// first-touch reads of a cold L2, ~2 us each, overlapped instead of chained)
-template <int K>
-struct PmWave { u32 id[K]; u32 hraw[PM_HEAD]; u32 sb, hd, lw; };
-template <int K>
-__device__ __forceinline__ void pm_wave_load(const PmSide& s, u32 c, PmWave<K>& w) {
-  const uint4* p = reinterpret_cast<const uint4*>(s.stream + (u64)c * (64 * K) + lane_id() * K);
-#pragma unroll
-  for (int q = 0; q < K / 4; q++) { const uint4 x = p[q]; w.id[4 * q] = x.x; w.id[4 * q + 1] = x.y; w.id[4 * q + 2] = x.z; w.id[4 * q + 3] = x.w; }
-  // the 64 * PM_HEAD entries before the chunk (the stream has that much padding in front): which of them belong to the
-  // segment that crosses into the chunk is known once head[c] is here, their addresses do not depend on it
-  const u32* hb = s.stream + (u64)c * (64 * K) + lane_id();
-#pragma unroll
-  for (int i = 0; i < PM_HEAD; i++) w.hraw[i] = *(hb - 64 * (i + 1));
-  w.sb = s.seg_base[c];
-  w.hd = s.head[c];
-  w.lw = s.lane_word[(u64)c * 64 + lane_id()];
-}
-// where the value of an entry comes from (the blocked passes of an oversized component read a block of the vector out of LDS instead)
-struct PmSrcGlobal {
-  const double* __restrict__ p;
-  __device__ __forceinline__ double operator()(u32 id) const { return p[id & ~PM_END]; }
-};
-template <int K, int PRE, bool WIN, class Emit, class Src>
-__device__ __forceinline__ void pm_wave_pass(const PmSide& s, u32 c, PmWave<K>& w, const Src& src, double* lds, const Emit& em) {
-  const int lane = lane_id();
-  u32 (&id)[K] = w.id;
-  const u32 sb = w.sb;
-  const u32 hd = w.hd;
-  const bool heavy = (hd & PM_HEAVY) != 0;
-  const bool longhead = !heavy && (hd & PM_LONG) != 0;
-  const u32 hlen = heavy ? 0u : (hd & ~PM_LONG);
-  // lane l holds the entries 64 * (i + 1) - l before the chunk
-  // A LONG head (a row / column of hundreds to thousands of entries that crosses into the chunk: repeat-family and poly-A classes, hub
-  // transcripts) is re-read in a loop, 64 entries per trip -- the trips are independent, so the chunk pays one more latency and a few
-  // dozen issue slots, where the fix-up launch it replaces cost a kernel boundary and a launch per direction and round (4.7 + 4.6 us
-  // each on the stress workload: 4 launches per round -> 2).  The entries are summed lane-strided, then across the lanes: a fixed order.
-  auto head_sum = [&](void) -> double {
-    double hv[PM_HEAD];
-#pragma unroll
-    for (int i = 0; i < PM_HEAD; i++) hv[i] = src(w.hraw[i]);
-    double hs = 0.0;
-#pragma unroll
-    for (int i = 0; i < PM_HEAD; i++) hs += (u32)(64 * (i + 1) - lane) <= hlen ? hv[i] : 0.0;
-    if (longhead) {
-      const u32* before = s.stream + (u64)c * (64 * K);   // entry i of the head (counted backwards from the chunk) at before[-1 - i]
-      u32 i = 64 * PM_HEAD + (u32)lane;
-      for (; i + 192 < hlen; i += 256) {   // four independent gathers per trip
-        const u32 i0 = before[-1 - (long)i], i1 = before[-1 - (long)(i + 64)], i2 = before[-1 - (long)(i + 128)], i3 = before[-1 - (long)(i + 192)];
-        const double v0 = src(i0), v1 = src(i1), v2 = src(i2), v3 = src(i3);
-        hs += v0; hs += v1; hs += v2; hs += v3;
-      }
-      for (; i < hlen; i += 64) hs += src(before[-1 - (long)i]);
-    }
-    return hs;
-  };
-  const u32 skip = heavy ? 1u : 0u;   // a heavy crossing segment's end is finished by pm_fix
-  // (the END flag stays in id[k]: its sign is the "this entry ends a segment" test of the loops below)
-  if constexpr (!WIN) {
-    const u32 ebase = w.lw & 0xFFFu, ne = (w.lw >> 12) & 0x3Fu;
-    const int reach = (int)(w.lw >> 18);
-    const u32 n_ends = (u32)__builtin_amdgcn_readlane((int)(ebase + ne), 63);
-    // every segment end of the chunk has its own LDS slot (all real chunks): no window tests, and the lane's first end is
-    // staged like the others and completed in place once the carry is known -- 6 instructions per entry instead of ~25
-    double v[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = src(id[k]);
-    double hsum = head_sum();
-    typename Emit::Ctx pre[PRE];
-#pragma unroll
-    for (int i = 0; i < PRE; i++) { const u32 j = skip + lane + 64 * i; if (j < n_ends) pre[i] = em.load(sb + j); }
-    if (hlen) hsum = pm_wave_sum(hsum);
-    double run = 0.0;
-    double* slot = lds + ebase;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-      run += v[k];
-      if ((int32_t)id[k] < 0) { *slot++ = run; run = 0.0; }
-    }
-    const double y = pm_scan_seg(run, reach, lane);
-    double carry = pm_dpp<0x138, 0xF>(y);   // wave_shr:1 (lane 0 gets 0)
-    if (ebase == 0) carry += hsum;
-    if (ne) {   // the lane's first end: what the lanes below it hold of that segment comes first in the sum
-      const double first = carry + lds[ebase];
-      lds[ebase] = first;
-      if (heavy && ebase == 0) s.lp[c] = first;
-    }
-    if (lane == 63) { if (n_ends == 0) { s.lp[c] = y; s.rp[c] = y; } else s.rp[c] = y; }
-    if (skip >= n_ends) return;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int i = 0; i < PRE; i++) { const u32 t = skip + lane + 64 * i; if (t < n_ends) em.finish(sb + t, pre[i], lds[t]); }
-    for (u32 t = skip + lane + 64 * PRE; t < n_ends; t += 128) {
-      const u32 t1 = t + 64;
-      const bool h1 = t1 < n_ends;
-      const typename Emit::Ctx x0 = em.load(sb + t), x1 = h1 ? em.load(sb + t1) : x0;
-      em.finish(sb + t, x0, lds[t]);
-      if (h1) em.finish(sb + t1, x1, lds[t1]);
-    }
-    return;
-  } else {
-  u32 ne = 0;
-#pragma unroll
-  for (int k = 0; k < K; k++) ne += id[k] >> 31;
-  const u32 incl = pm_scan_incl(ne);   // segment ends in this and the lower lanes
-  const u32 ebase = incl - ne;
-  const u32 n_ends = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-  const u64 heads = __ballot(ne > 0);
-  // (one window unless the chunk holds more segment ends than the wavefront's share of LDS; then the pass is repeated)
-  for (u32 w0 = skip; w0 == skip || w0 < n_ends; w0 += PM_LDS_SLOTS) {
-    double v[K];
-#pragma unroll
-    for (int k = 0; k < K; k++) v[k] = src(id[k]);
-    double hsum = head_sum();
-    typename Emit::Ctx pre[PRE];
-#pragma unroll
-    for (int i = 0; i < PRE; i++) { const u32 j = w0 + lane + 64 * i; if (j < n_ends) pre[i] = em.load(sb + j); }
-    if (hlen) hsum = pm_wave_sum(hsum);
-    // lane-local pass in entry order: a segment that ends after an earlier end of the same lane is complete -> staged in LDS
-    // at its local index; the sum up to the lane's first end waits for the carry; the open tail feeds the wavefront scan
-    double run = 0.0, first_part = 0.0;
-    bool got = false;
-    u32 j = ebase;
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-      run += v[k];
-      if ((int32_t)id[k] < 0) {
-        if (!got) { first_part = run; got = true; }
-        else if (j >= w0 && j < w0 + PM_LDS_SLOTS) lds[j - w0] = run;
-        ++j; run = 0.0;
-      }
-    }
-    double y = run;   // segmented inclusive scan; a lane that holds a segment end starts a new run with its tail
-    // lane may add the partial sum of lane - d iff no lane in (lane - d, lane] holds an end, i.e. iff d <= its distance to the
-    // nearest end at or below it (the lane itself: 0; none: lane + 1 -- which also covers the lane >= d test)
-    const u64 below = heads & ((2ULL << lane) - 1ULL);
-    const int reach = below ? lane - (63 - __clzll((long long)below)) : lane + 1;
-    y = pm_scan_seg(y, reach, lane);
-    double carry = pm_dpp<0x138, 0xF>(y);   // wave_shr:1 (lane 0 gets 0)
-    if (ebase == 0) carry += hsum;   // the chunk's first end also gets the re-read head
-    if (got && ebase >= w0 && ebase < w0 + PM_LDS_SLOTS) lds[ebase - w0] = carry + first_part;
-    if (w0 == skip) {  // partial sums for pm_fix: a chunk without any end lies wholly inside one segment (its sum is both)
-      if (lane == 63) { if (n_ends == 0) { s.lp[c] = y; s.rp[c] = y; } else s.rp[c] = y; }
-      if (heavy && got && ebase == 0) s.lp[c] = carry + first_part;
-    }
-    if (w0 >= n_ends) break;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const u32 wn = min(n_ends - w0, (u32)PM_LDS_SLOTS);
-#pragma unroll
-    for (int i = 0; i < PRE; i++) { const u32 t = lane + 64 * i; if (t < wn) em.finish(sb + w0 + t, pre[i], lds[t]); }
-    for (u32 t = lane + 64 * PRE; t < wn; t += 128) {   // beyond the prefetched contexts: two segments per lane and trip
-      const u32 t1 = t + 64;
-      const bool h1 = t1 < wn;
-      const typename Emit::Ctx x0 = em.load(sb + w0 + t), x1 = h1 ? em.load(sb + w0 + t1) : x0;
-      em.finish(sb + w0 + t, x0, lds[t]);
-      if (h1) em.finish(sb + w0 + t1, x1, lds[t1]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  }
-}
-// a heavy crossing segment that ends in chunk c: right partial of the chunk it started in + the chunks wholly inside it +
-// this chunk's left partial, in chunk order; one thread per chunk
-template <class Emit>
-__device__ __forceinline__ void pm_fix(const PmSide& s, u32 c, const Emit& em) {
-  if (c >= s.n_chunks) return;
-  const u32 f = s.fix_first[c];
-  if (f == PM_NONE) return;
-  const u32 seg = s.seg_base[c];
-  const typename Emit::Ctx cx = em.load(seg);
-  double S = s.rp[f];
-  for (u32 k = f + 1; k < c; k++) S += s.lp[k];
-  S += s.lp[c];
-  em.finish(seg, cx, S);
-}
-// change counter of the round: one atomic per block
-__device__ __forceinline__ void pm_count_changes(int ch, int* lds_ch, EmState* rec) {
-  if (threadIdx.x == 0) *lds_ch = 0;
-  __syncthreads();
-  if (__ballot(ch != 0)) {
-    int wsum = ch;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) wsum += __shfl_down(wsum, d, 64);
-    if (lane_id() == 0) atomicAdd(lds_ch, wsum);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0 && *lds_ch) atomicAdd(&rec->chcount, *lds_ch);
-}
-
-// rows launch (first of the round: block 0 publishes the round's loop-control record, like k_em_rows)
-template <int K, int PRE, bool WIN>
-__global__ __launch_bounds__(PM_BLOCK) void k_pm_rows_pass(PmArgs A, int parity) {
-  __shared__ double lds_sums[(PM_BLOCK / 64) * PM_LDS_SLOTS];
-  const EmState prev = A.st[parity ^ 1];
-  const u32 c = __builtin_amdgcn_readfirstlane(blockIdx.x * (PM_BLOCK / 64) + (threadIdx.x >> 6));
-  PmWave<K> w;
-  if (c < A.rows.n_chunks) pm_wave_load<K>(A.rows, c, w);
-  const EmNow now = em_next_round(prev, A.n_iter, A.min_rounds, A.spec_hist != nullptr);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    EmState r; r.iter = now.it; r.chcount = 0; r.final_round = now.fin; r.done = now.done; r.rounds = now.rounds; r.force_final = 0;
-    r.pad[0] = r.pad[1] = 0;
-    A.st[parity] = r;
-    if (A.spec_hist && !prev.done && prev.iter >= 0) A.spec_hist[prev.iter] = prev.chcount;
-  }
-  if (now.done) return;
-  const int odd = now.it & 1;
-  if (c >= A.rows.n_chunks) return;
-  const PmRowEmit em{A.cw, A.g};
-  const double* a_cur = now.fin ? (odd ? A.ac1 : A.ac0) : (odd ? A.a1 : A.a0);
-  pm_wave_pass<K, PRE, WIN>(A.rows, c, w, PmSrcGlobal{a_cur}, lds_sums + (threadIdx.x >> 6) * PM_LDS_SLOTS, em);
-}
-template <int K, int PRE, bool WIN>
-__global__ __launch_bounds__(PM_BLOCK) void k_pm_cols_pass(PmArgs A, int parity) {
-  __shared__ double lds_sums[(PM_BLOCK / 64) * PM_LDS_SLOTS];
-  __shared__ int lds_ch;
-  const EmState prev = A.st[parity ^ 1];
-  const u32 c = __builtin_amdgcn_readfirstlane(blockIdx.x * (PM_BLOCK / 64) + (threadIdx.x >> 6));
-  PmWave<K> w;
-  if (c < A.cols.n_chunks) pm_wave_load<K>(A.cols, c, w);
-  const EmNow now = em_next_round(prev, A.n_iter, A.min_rounds, A.spec_hist != nullptr);
-  if (now.done) return;
-  const int odd = now.it & 1;
-  int ch = 0;
-  const double* a_cur = now.fin ? (odd ? A.ac1 : A.ac0) : (odd ? A.a1 : A.a0);
-  const PmColEmit em{odd ? A.alpha1 : A.alpha0, a_cur, A.single, A.eff, odd ? A.alpha0 : A.alpha1, odd ? A.a0 : A.a1, odd ? A.ac0 : A.ac1, &ch, now.fin};
-  if (c < A.cols.n_chunks) pm_wave_pass<K, PRE, WIN>(A.cols, c, w, PmSrcGlobal{A.g}, lds_sums + (threadIdx.x >> 6) * PM_LDS_SLOTS, em);
-  pm_count_changes(ch, &lds_ch, &A.st[parity]);
-}
-// fix-up launches (only enqueued when a direction has heavy crossing segments)
-__global__ __launch_bounds__(PM_BLOCK) void k_pm_rows_fix(PmArgs A, int parity) {
-  if (em_next_round(A.st[parity ^ 1], A.n_iter, A.min_rounds, A.spec_hist != nullptr).done) return;
-  const PmRowEmit em{A.cw, A.g};
-  pm_fix(A.rows, blockIdx.x * PM_BLOCK + threadIdx.x, em);
-}
-__global__ __launch_bounds__(PM_BLOCK) void k_pm_cols_fix(PmArgs A, int parity) {
-  __shared__ int lds_ch;
-  const EmNow now = em_next_round(A.st[parity ^ 1], A.n_iter, A.min_rounds, A.spec_hist != nullptr);
-  if (now.done) return;
-  const int odd = now.it & 1;
-  int ch = 0;
-  const double* a_cur = now.fin ? (odd ? A.ac1 : A.ac0) : (odd ? A.a1 : A.a0);
-  const PmColEmit em{odd ? A.alpha1 : A.alpha0, a_cur, A.single, A.eff, odd ? A.alpha0 : A.alpha1, odd ? A.a0 : A.a1, odd ? A.ac0 : A.ac1, &ch, now.fin};
-  pm_fix(A.cols, blockIdx.x * PM_BLOCK + threadIdx.x, em);
-  pm_count_changes(ch, &lds_ch, &A.st[parity]);
-}
-
-// ---- one-time re-layout for the streamed form -------------------------------------------------------------------------
-// Kept rows are renumbered by their smallest transcript id (a counting sort): rows of one gene become neighbours, and since
-// the isoforms of a gene are neighbours in transcript space too, the 8-byte gathers of a wavefront fall into few cache
-// lines (the passes are bound by the L2 request rate of uncoalesced gathers, not by bytes).
-__global__ void k_pm_flags(const u64* __restrict__ ec_off, const u32* __restrict__ ec_ids, u64 n_ecs, const u32* __restrict__ col_cnt, u64 n_tr,
-                           u32* hist, u32* mflag) {
-  const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_ecs) { const u64 a = ec_off[i]; if (ec_off[i + 1] - a >= 2) atomicAdd(&hist[ec_ids[a]], 1u); }   // sets are sorted: first = smallest
-  if (i < n_tr) mflag[i] = col_cnt[i] ? 1u : 0u;
-}
-// The new number of a kept row: rows ordered by the bucket of their smallest transcript (4096 buckets over the transcripts: rows of one gene
-// become neighbours, the gathers of a wavefront fall into few lines and a row block of the blocked form holds few genes' rows), rows of one
-// bucket by a 48-bit hash of their CONTENT (the set of transcripts; equal sets do not occur).  The numbering -- and with it the order of every
-// floating-point sum of the streamed and blocked forms -- is therefore a function of the matrix alone, whatever order kamd_ec_finalize's
-// atomics emitted the classes in (until round 5 the place inside a group came from an atomic counter: abundances of an oversized component
-// differed in the last bits from run to run).  A least-significant-digit radix sort of the rows by that 60-bit key, 12 bits per pass; a pass
-// is a STABLE counting sort: one wavefront per tile of PM_RANK_TILE rows counts its rows per digit (k_pm_radix_hist), a scan over (digit, tile)
-// gives every tile's first place in every digit, k_pm_radix_place walks the tile in order, 64 rows at a time.  Rows that are not kept (fewer
-// than two transcripts) carry the largest key and end up behind the R kept ones.
-constexpr int PM_RANK_BUCKETS = 4096, PM_RANK_TILE = 1024, PM_RANK_PASSES = 5;
-__global__ void k_pm_rowkey(const u64* __restrict__ ec_off, const u32* __restrict__ ec_ids, u64 n_ecs, u64 n_tr, u64* key) {
-  const u64 e = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / 8;   // 8 lanes per row
-  const int sub = threadIdx.x & 7;
-  if (e >= n_ecs) return;
-  const u64 a = ec_off[e], b = ec_off[e + 1];
-  u64 h = 0;
-  for (u64 j = a + sub; j < b; j += 8) h += kamd::mix64((u64)ec_ids[j] + 0x9e3779b97f4a7c15ULL);   // (a sum: the same for any order of the members)
-  h += shfl_u64(h, lane_id() ^ 1); h += shfl_u64(h, lane_id() ^ 2); h += shfl_u64(h, lane_id() ^ 4);
-  if (sub == 0) key[e] = b - a >= 2 ? (((u64)ec_ids[a] * PM_RANK_BUCKETS / n_tr) << 48) | (kamd::mix64(h) >> 16) : ~0ULL;
-}
-__device__ __forceinline__ u32 pm_radix_digit(u64 k, int pass) { return (u32)(k >> (12 * pass)) & (PM_RANK_BUCKETS - 1); }
-// order_in == null: the identity (first pass)
-__global__ __launch_bounds__(64) void k_pm_radix_hist(const u64* __restrict__ key, const u32* __restrict__ order_in, u64 n, int pass, u32 n_tiles, u32* hist) {
-  __shared__ u32 s_cnt[PM_RANK_BUCKETS];
-  const int lane = lane_id();
-  for (int i = lane; i < PM_RANK_BUCKETS; i += 64) s_cnt[i] = 0u;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const u64 p0 = (u64)blockIdx.x * PM_RANK_TILE;
-  for (u32 i = lane; i < (u32)PM_RANK_TILE; i += 64) {
-    const u64 p = p0 + i;
-    if (p < n) atomicAdd(&s_cnt[pm_radix_digit(key[order_in ? order_in[p] : p], pass)], 1u);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  for (int i = lane; i < PM_RANK_BUCKETS; i += 64) hist[(u64)i * n_tiles + blockIdx.x] = s_cnt[i];
-}
-__global__ __launch_bounds__(64) void k_pm_radix_place(const u64* __restrict__ key, const u32* __restrict__ order_in, u64 n, int pass, u32 n_tiles,
-                                                       const u64* __restrict__ first, u32* order_out) {
-  __shared__ u32 s_cnt[PM_RANK_BUCKETS];   // rows of the tile placed so far, per digit
-  const int lane = lane_id();
-  for (int i = lane; i < PM_RANK_BUCKETS; i += 64) s_cnt[i] = 0u;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  const u64 p0 = (u64)blockIdx.x * PM_RANK_TILE;
-  for (u32 i0 = 0; i0 < (u32)PM_RANK_TILE; i0 += 64) {
-    const u64 p = p0 + i0 + lane;
-    const bool in = p < n;
-    const u32 e = in ? (order_in ? order_in[p] : (u32)p) : 0u;
-    const u32 dg = in ? pm_radix_digit(key[e], pass) : 0xFFFFFFFFu;
-    // the lanes of one digit, in lane order: one leader per distinct digit and trip
-    u64 todo = __ballot(in);
-    u32 before = 0, same_total = 0;
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const u32 ld = (u32)__shfl((int)dg, leader, 64);
-      const u64 same = __ballot(dg == ld);
-      if (dg == ld) { before = (u32)__popcll(same & ((1ULL << lane) - 1ULL)); same_total = (u32)__popcll(same); }
-      todo &= ~same;
-    }
-    if (in) order_out[first[(u64)dg * n_tiles + blockIdx.x] + s_cnt[dg] + before] = e;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (in && before == 0) s_cnt[dg] += same_total;   // (the first lane of every digit)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-}
-// the sorted order -> the kept rows' new numbers and lengths (the R kept rows come first)
-__global__ void k_pm_rank_emit(const u64* __restrict__ ec_off, const u32* __restrict__ order, u64 R, u64* rpos, u32* len_sorted) {
-  const u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  const u32 e = order[r];
-  rpos[e] = r;
-  len_sorted[r] = (u32)(ec_off[e + 1] - ec_off[e]);
-}
-// kept row e -> entries of the row stream, its count word and offset; 8 lanes per row
-__global__ void k_pm_rows(const u64* __restrict__ ec_off, const u32* __restrict__ ec_ids, const u32* __restrict__ counts,
-                          const u32* __restrict__ wcounts, u64 n_ecs, const u64* __restrict__ rpos, const u64* __restrict__ roff,
-                          const u64* __restrict__ mpos, u32* stream, u64* cw) {
-  const u64 e = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / 8;
-  const int sub = threadIdx.x & 7;
-  if (e >= n_ecs) return;
-  const u64 a = ec_off[e], b = ec_off[e + 1];
-  if (b - a < 2) return;
-  const u64 r = rpos[e], base = roff[r];
-  for (u64 j = a + sub; j < b; j += 8) stream[base + (j - a)] = (u32)mpos[ec_ids[j]] | (j + 1 == b ? PM_END : 0u);
-  if (sub == 0) cw[r] = (u64)counts[e] | ((u64)wcounts[e] << 32);
-}
-__global__ void k_pm_cols(const u64* __restrict__ ec_off, const u32* __restrict__ ec_ids, u64 n_ecs, const u64* __restrict__ rpos,
-                          const u64* __restrict__ col_off, u32* col_fill, u32* stream) {
-  const u64 e = ((u64)blockIdx.x * blockDim.x + threadIdx.x) / 8;
-  const int sub = threadIdx.x & 7;
-  if (e >= n_ecs) return;
-  const u64 a = ec_off[e], b = ec_off[e + 1];
-  if (b - a < 2) return;
-  const u32 r = (u32)rpos[e];
-  for (u64 j = a + sub; j < b; j += 8) {
-    const u32 t = ec_ids[j];
-    const u64 p = col_off[t] + atomicAdd(&col_fill[t], 1u);
-    stream[p] = r | (p + 1 == col_off[t + 1] ? PM_END : 0u);
-  }
-}
-__global__ void k_pm_fill(u32* p, u64 a, u64 b, u32 v) {
-  const u64 i = a + (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < b) p[i] = v;
-}
-// m-space vectors; alpha_ = 1/T for every transcript (:38)
-__global__ void k_pm_minit(u64 n_tr, const u32* __restrict__ mflag, const u64* __restrict__ mpos, const u64* __restrict__ col_off,
-                           const double* __restrict__ single, const double* __restrict__ eff, u64 M, u64* coff, double* single_m,
-                           double* eff_m, double* alpha0, double* alpha1, double* a0, double* a1, double* ac0, double* ac1) {
-  const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) { if (coff) coff[M] = col_off[n_tr]; alpha0[M] = alpha1[M] = a0[M] = a1[M] = ac0[M] = ac1[M] = 0.0; }
-  if (t >= n_tr || !mflag[t]) return;
-  const u64 m = mpos[t];
-  if (coff) coff[m] = col_off[t];   // (null: a cached plan gets new counts and effective lengths, its layout stays)
-  single_m[m] = single[t]; eff_m[m] = eff[t];
-  const double al = 1.0 / (double)n_tr;
-  alpha0[m] = al; a0[m] = al / eff[t]; alpha1[m] = 0.0; a1[m] = 0.0;
-  ac0[m] = al < 1e-7 / 10.0 ? 0.0 : al / eff[t]; ac1[m] = 0.0;
-}
-// per chunk: the segment its first entry belongs to (binary search in the segment offsets) and how it is completed
-__global__ void k_pm_chunks(const u64* __restrict__ off, u64 n_seg, u64 nz, u32 chunk, u32 n_chunks, u32* seg_base, u32* head,
-                            u32* fix_first, u32* n_fix, u32* max_ends, int no_long) {
-  const u32 c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_chunks) return;
-  const u64 c0 = (u64)c * chunk, c1 = c0 + chunk;
-  u64 lo = 0, hi = n_seg;  // largest s in [0, n_seg) with off[s] <= c0 (off[0] = 0, offsets strictly increase)
-  while (hi - lo > 1) { const u64 mid = (lo + hi) / 2; if (off[mid] <= c0) lo = mid; else hi = mid; }
-  const u64 hs = off[lo], se = off[lo + 1];
-  const u64 hl = c0 - hs;  // entries of the segment before the chunk
-  // (a long head is only re-read by the chunk the segment ENDS in: a chunk wholly inside the segment would gather its hl preceding entries every
-  // round and throw the sum away -- O(L^2 / chunk) wasted gathers per long segment; such chunks are marked heavy and need nothing but their own sum)
-  const bool is_long = hl > 64ULL * PM_HEAD && hl <= (u64)PM_LOOP_MAX && !no_long && se <= c1;
-  const bool is_heavy = hl > 64ULL * PM_HEAD && !is_long;
-  seg_base[c] = (u32)lo;
-  head[c] = hl == 0 ? 0u : (is_heavy ? PM_HEAVY : (is_long ? (PM_LONG | (u32)hl) : (u32)hl));
-  const bool fix = is_heavy && se <= c1;
-  fix_first[c] = fix ? (u32)(hs / chunk) : PM_NONE;
-  if (fix) atomicAdd(n_fix, 1u);
-  const u64 ce = c1 < nz ? c1 : nz;   // segment ends inside the chunk: segments lo .. l2 - 1, l2 = largest s in [0, n_seg] with off[s] <= ce
-  u64 l2 = lo; hi = n_seg + 1;
-  while (hi - l2 > 1) { const u64 mid = (l2 + hi) / 2; if (off[mid] <= ce) l2 = mid; else hi = mid; }
-  if (l2 - lo > (u64)PM_LDS_SLOTS) atomicMax(max_ends, (u32)(l2 - lo));
-}
-// per lane of every chunk: PmSide::lane_word; one wavefront per chunk, any K
-__global__ __launch_bounds__(PM_BLOCK) void k_pm_lanes(const u32* __restrict__ stream, u32 k, u32 n_chunks, u32* lane_word) {
-  const u32 c = blockIdx.x * (PM_BLOCK / 64) + (threadIdx.x >> 6);
-  if (c >= n_chunks) return;
-  const int lane = lane_id();
-  const u32* p = stream + (u64)c * (64 * k) + (u64)lane * k;
-  u32 ne = 0;
-  for (u32 i = 0; i < k; i++) ne += p[i] >> 31;
-  const u32 incl = pm_scan_incl(ne);
-  const u64 heads = __ballot(ne > 0);
-  const u64 below = heads & ((2ULL << lane) - 1ULL);
-  const u32 reach = below ? (u32)(lane - (63 - __clzll((long long)below))) : (u32)(lane + 1);
-  lane_word[(u64)c * 64 + lane] = (incl - ne) | (ne << 12) | (reach << 18);
-}
 // back to transcript space: both buffers (result and alpha_before_zeroes are picked by the caller).  A transcript that
 // only has a singleton set holds that count in every buffer from round 1 on; one that is in no set stays 0.
 __global__ void k_pm_scatter(u64 n_tr, const u32* __restrict__ mflag, const u64* __restrict__ mpos, const double* __restrict__ single,
@@ -882,184 +327,6 @@ extern "C" int kamd_em_run_partitioned(kamd_ctx* c, uint32_t rank, uint32_t worl
 }
 
 namespace {
-// ---- streamed EM: re-layout of the matrix (once per run) and the per-round launches -------------------------------------
-struct Carver {  // sub-allocations of one device arena, 256-byte aligned
-  size_t off = 0;
-  size_t take(size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; }
-};
-struct PmPlan {
-  PmArgs args{};
-  int k = 0;                 // entries per lane
-  bool windowed = false;     // some chunk holds more segment ends than a wavefront's LDS slots (or KAMD_EM_WINDOWED=1): the general pass
-  u32 n_chunks = 0;
-  u32 n_fix[2] = {0, 0};     // heavy crossing segments per direction (0: no fix-up launch)
-  const u32* mflag = nullptr; const u64* mpos = nullptr;   // transcript -> m-space
-  const u64* roff = nullptr; const u64* coff = nullptr;    // [R + 1] / [M + 1] entry offsets of the rows / columns (the hybrid picks its hot targets by length)
-  u32* rs = nullptr; u32* cs = nullptr; u64 nzpad = 0;     // the two entry streams (nzpad entries each)
-  const u64* rpos = nullptr;                               // row of the source matrix -> kept row (rows of fewer than two transcripts: unset)
-};
-constexpr int PM_KS[] = {8, 12, 16, 20, 24, 28, 32};
-template <int K>
-void pm_launch_round(const PmPlan& P, hipStream_t s, int parity) {
-  const unsigned grid = grid_for(P.n_chunks, PM_BLOCK / 64);
-  constexpr int PRE_R = (K + 5) / 6 < 2 ? 2 : (K + 5) / 6;   // 64 * PRE >= ~chunk / 6 row ends
-  constexpr int PRE_C = K / 16 + 1;                           // 64 * PRE >= ~chunk / 16 column ends
-  if (P.windowed) hipLaunchKernelGGL((k_pm_rows_pass<K, PRE_R, true>), dim3(grid), dim3(PM_BLOCK), 0, s, P.args, parity);
-  else hipLaunchKernelGGL((k_pm_rows_pass<K, PRE_R, false>), dim3(grid), dim3(PM_BLOCK), 0, s, P.args, parity);
-  if (P.n_fix[0]) hipLaunchKernelGGL(k_pm_rows_fix, dim3(grid_for(P.n_chunks, PM_BLOCK)), dim3(PM_BLOCK), 0, s, P.args, parity);
-  if (P.windowed) hipLaunchKernelGGL((k_pm_cols_pass<K, PRE_C, true>), dim3(grid), dim3(PM_BLOCK), 0, s, P.args, parity);
-  else hipLaunchKernelGGL((k_pm_cols_pass<K, PRE_C, false>), dim3(grid), dim3(PM_BLOCK), 0, s, P.args, parity);
-  if (P.n_fix[1]) hipLaunchKernelGGL(k_pm_cols_fix, dim3(grid_for(P.n_chunks, PM_BLOCK)), dim3(PM_BLOCK), 0, s, P.args, parity);
-}
-void pm_enqueue_round(const PmPlan& P, hipStream_t s, int parity) {
-  switch (P.k) {
-    case 8: pm_launch_round<8>(P, s, parity); break;
-    case 12: pm_launch_round<12>(P, s, parity); break;
-    case 16: pm_launch_round<16>(P, s, parity); break;
-    case 20: pm_launch_round<20>(P, s, parity); break;
-    case 24: pm_launch_round<24>(P, s, parity); break;
-    case 28: pm_launch_round<28>(P, s, parity); break;
-    default: pm_launch_round<32>(P, s, parity); break;
-  }
-}
-
-// returns 0 = plan built (the rounds can be enqueued with pm_enqueue_round), 1 = not applicable (the caller uses the CSR
-// form), < 0 = error.  Needs col_cnt / em_coloff / em_single / em_eff of the caller (k_em_prepare + scan) and a zeroed col_fill.
-int em_streamed_setup(kamd_ctx* c, const u64* ec_off, const u32* ec_ids, const u32* counts, const u32* wcounts, u64 n_ecs, u64 T,
-                      const u32* col_cnt, u32* col_fill, PmPlan* P, DBuf* arena_a = nullptr, DBuf* arena_b = nullptr) {
-  if (n_ecs == 0) return 1;
-  DBuf& ar_a = arena_a ? *arena_a : c->pm_a;   // (the hybrid keeps the streamed plan of the oversized components in arenas of its own: pm_a / pm_b
-  DBuf& ar_b = arena_b ? *arena_b : c->pm_b;   //  hold the LDS form's plan and vectors at the same time)
-  if (c->n_cus == 0) {
-    int v = 0;
-    HIPC(hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device));
-    c->n_cus = v > 0 ? v : 256;
-  }
-  // stage 1: which rows / transcripts are kept, and their new numbers (rows: counting sort by smallest transcript)
-  Carver s1;
-  const size_t o_hist = s1.take((T + 1) * 4), o_fill = s1.take((T + 1) * 4), o_mflag = s1.take(T * 4);
-  const size_t o_start = s1.take((T + 2) * 8), o_rpos = s1.take((n_ecs + 1) * 8), o_mpos = s1.take((T + 1) * 8);
-  const size_t o_len = s1.take((n_ecs + 1) * 4), o_roff = s1.take((n_ecs + 2) * 8);
-  if (int rc = ar_a.ensure(s1.off, 0, c->stream)) return rc;
-  char* b1 = (char*)ar_a.p;
-  u32* hist = (u32*)(b1 + o_hist); u32* mflag = (u32*)(b1 + o_mflag);
-  u64* start = (u64*)(b1 + o_start); u64* rpos = (u64*)(b1 + o_rpos); u64* mpos = (u64*)(b1 + o_mpos);
-  u32* len_sorted = (u32*)(b1 + o_len); u64* roff = (u64*)(b1 + o_roff);
-  (void)o_fill;
-  HIPC(hipMemsetAsync(hist, 0, (o_mflag - o_hist), c->stream));
-  hipLaunchKernelGGL(k_pm_flags, dim3(grid_for(std::max(n_ecs, T), BLOCK)), dim3(BLOCK), 0, c->stream, ec_off, ec_ids, n_ecs, col_cnt, T, hist,
-                     mflag);
-  if (int rc = exclusive_scan(c, hist, T, start, start + T)) return rc;
-  if (int rc = exclusive_scan(c, mflag, T, mpos, mpos + T)) return rc;
-  u64 R = 0, NZ = 0, M = 0;
-  HIPC(hipMemcpyAsync(&R, start + T, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(&M, mpos + T, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipMemcpyAsync(&NZ, c->em_coloff.as<u64>() + T, 8, hipMemcpyDeviceToHost, c->stream));   // non-zeros of the kept rows
-  HIPC(hipStreamSynchronize(c->stream));
-  if (NZ == 0 || R == 0 || M == 0 || R >= 0x7FFFFFF0ULL || M >= 0x7FFFFFF0ULL || NZ >= (1ULL << 40)) return 1;
-  {
-    if (n_ecs >= 0xFFFFFFF0ULL) return 1;
-    const u32 n_tiles = (u32)((n_ecs + PM_RANK_TILE - 1) / PM_RANK_TILE);
-    const u64 n_cells = (u64)PM_RANK_BUCKETS * n_tiles;
-    Carver rv;
-    const size_t o_key = rv.take(n_ecs * 8), o_oa = rv.take(n_ecs * 4), o_ob = rv.take(n_ecs * 4), o_h = rv.take(n_cells * 4), o_f = rv.take((n_cells + 2) * 8);
-    if (int rc = c->pm_rank.ensure(rv.off, 0, c->stream)) return rc;
-    char* rb = (char*)c->pm_rank.p;
-    u64* key = (u64*)(rb + o_key); u32* ord[2] = {(u32*)(rb + o_oa), (u32*)(rb + o_ob)}; u32* rhist = (u32*)(rb + o_h); u64* rfirst = (u64*)(rb + o_f);
-    hipLaunchKernelGGL(k_pm_rowkey, dim3(grid_for(n_ecs * 8, BLOCK)), dim3(BLOCK), 0, c->stream, ec_off, ec_ids, n_ecs, T, key);
-    const u32* in = nullptr;
-    for (int pass = 0; pass < PM_RANK_PASSES; pass++) {
-      u32* out = ord[pass & 1];
-      hipLaunchKernelGGL(k_pm_radix_hist, dim3(n_tiles), dim3(64), 0, c->stream, (const u64*)key, in, n_ecs, pass, n_tiles, rhist);
-      if (int rc = exclusive_scan(c, rhist, n_cells, rfirst, rfirst + n_cells)) return rc;
-      hipLaunchKernelGGL(k_pm_radix_place, dim3(n_tiles), dim3(64), 0, c->stream, (const u64*)key, in, n_ecs, pass, n_tiles, (const u64*)rfirst, out);
-      in = out;
-    }
-    hipLaunchKernelGGL(k_pm_rank_emit, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, c->stream, ec_off, in, R, rpos, len_sorted);
-    HIPC(hipGetLastError());
-  }
-  if (int rc = exclusive_scan(c, len_sorted, R, roff, roff + R)) return rc;   // roff[R] = NZ
-  // entries per lane: the smallest K whose chunks fit the chip in one go at 12 wavefronts per CU (measured on config #3:
-  // 28.0 us per round at K = 24 / 3038 chunks against 32.7 at K = 20 / 3646 and 32.5 at K = 16 / 4557, same box)
-  int K = PM_KS[sizeof(PM_KS) / sizeof(PM_KS[0]) - 1];
-  bool k_forced = false;
-  if (c->tune.em_entries_per_lane > 0) { for (int k : PM_KS) if (k == c->tune.em_entries_per_lane) { K = k; k_forced = true; } }
-  if (!k_forced) for (int k : PM_KS) if ((NZ + 64ULL * k - 1) / (64ULL * k) <= (u64)c->n_cus * 12) { K = k; break; }
-  const u32 chunk = 64u * (u32)K;
-  const u64 n_chunks64 = (NZ + chunk - 1) / chunk;
-  if (n_chunks64 >= 0x7FFFFFF0ULL) return 1;
-  const u32 n_chunks = (u32)n_chunks64;
-  const u64 nzpad = (u64)n_chunks * chunk;
-  // stage 2
-  Carver s2;
-  const size_t front = 64 * PM_HEAD * 4;   // the passes read up to 64 * PM_HEAD entries before a chunk, also before chunk 0
-  const size_t o_rs = s2.take(front + nzpad * 4), o_cs = s2.take(front + nzpad * 4);
-  size_t o_meta[2][5];
-  size_t o_lane[2];
-  for (int s = 0; s < 2; s++) {
-    for (int j = 0; j < 3; j++) o_meta[s][j] = s2.take((size_t)n_chunks * 4);
-    for (int j = 3; j < 5; j++) o_meta[s][j] = s2.take((size_t)n_chunks * 8);
-    o_lane[s] = s2.take((size_t)n_chunks * 64 * 4);
-  }
-  const size_t o_cw = s2.take(R * 8), o_coff = s2.take((M + 1) * 8), o_g = s2.take((R + 1) * 8);
-  size_t o_vec[6];
-  for (int j = 0; j < 6; j++) o_vec[j] = s2.take((M + 1) * 8);
-  const size_t o_single = s2.take(M * 8), o_eff = s2.take(M * 8), o_nfix = s2.take(64);
-  if (int rc = ar_b.ensure(s2.off, 0, c->stream)) return rc;
-  char* b2 = (char*)ar_b.p;
-  u32* rs = (u32*)(b2 + o_rs + front); u32* cs = (u32*)(b2 + o_cs + front);
-  HIPC(hipMemsetAsync(b2 + o_rs, 0, front, c->stream));
-  HIPC(hipMemsetAsync(b2 + o_cs, 0, front, c->stream));
-  u64* cw = (u64*)(b2 + o_cw); u64* coff = (u64*)(b2 + o_coff);
-  double* g = (double*)(b2 + o_g);
-  double* vec[6]; for (int j = 0; j < 6; j++) vec[j] = (double*)(b2 + o_vec[j]);
-  double* single_m = (double*)(b2 + o_single); double* eff_m = (double*)(b2 + o_eff);
-  HIPC(hipMemsetAsync(b2 + o_nfix, 0, 64, c->stream));
-  HIPC(hipMemsetAsync(g + R, 0, 8, c->stream));
-  const u64* col_off = c->em_coloff.as<u64>();
-  hipLaunchKernelGGL(k_pm_rows, dim3(grid_for(n_ecs * 8, BLOCK)), dim3(BLOCK), 0, c->stream, ec_off, ec_ids, counts, wcounts, n_ecs, rpos, roff,
-                     mpos, rs, cw);
-  hipLaunchKernelGGL(k_pm_cols, dim3(grid_for(n_ecs * 8, BLOCK)), dim3(BLOCK), 0, c->stream, ec_off, ec_ids, n_ecs, rpos, col_off, col_fill, cs);
-  if (nzpad > NZ) {
-    hipLaunchKernelGGL(k_pm_fill, dim3(grid_for(nzpad - NZ, BLOCK)), dim3(BLOCK), 0, c->stream, rs, NZ, nzpad, (u32)M);
-    hipLaunchKernelGGL(k_pm_fill, dim3(grid_for(nzpad - NZ, BLOCK)), dim3(BLOCK), 0, c->stream, cs, NZ, nzpad, (u32)R);
-  }
-  hipLaunchKernelGGL(k_pm_minit, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, mflag, mpos, col_off, c->em_single.as<double>(),
-                     c->em_eff.as<double>(), M, coff, single_m, eff_m, vec[0], vec[1], vec[2], vec[3], vec[4], vec[5]);
-  PmSide sides[2];
-  for (int s = 0; s < 2; s++) {
-    PmSide& d = sides[s];
-    d.stream = s == 0 ? rs : cs;
-    u32* sb = (u32*)(b2 + o_meta[s][0]); u32* hd = (u32*)(b2 + o_meta[s][1]); u32* ff = (u32*)(b2 + o_meta[s][2]);
-    d.seg_base = sb; d.head = hd; d.fix_first = ff;
-    d.lp = (double*)(b2 + o_meta[s][3]); d.rp = (double*)(b2 + o_meta[s][4]);
-    d.n_chunks = n_chunks;
-    u32* lw = (u32*)(b2 + o_lane[s]);
-    d.lane_word = lw;
-    hipLaunchKernelGGL(k_pm_lanes, dim3(grid_for(n_chunks, PM_BLOCK / 64)), dim3(PM_BLOCK), 0, c->stream, d.stream, chunk / 64, n_chunks, lw);
-    hipLaunchKernelGGL(k_pm_chunks, dim3(grid_for(n_chunks, BLOCK)), dim3(BLOCK), 0, c->stream, s == 0 ? roff : coff, s == 0 ? R : M, NZ, chunk,
-                       n_chunks, sb, hd, ff, (u32*)(b2 + o_nfix) + s, (u32*)(b2 + o_nfix) + 2, getenv("KAMD_EM_NO_LONG_HEADS") ? 1 : 0);
-  }
-  HIPC(hipGetLastError());
-  PmArgs& A = P->args;
-  A.rows = sides[0]; A.cols = sides[1];
-  A.cw = cw; A.g = g;
-  A.alpha0 = vec[0]; A.alpha1 = vec[1]; A.a0 = vec[2]; A.a1 = vec[3]; A.ac0 = vec[4]; A.ac1 = vec[5];
-  A.single = single_m; A.eff = eff_m;
-  A.R = (u32)R; A.M = (u32)M;
-  A.st = (EmState*)c->em_state.p;
-  u32 plan_words[3] = {0, 0, 0};   // heavy crossings per direction, largest number of segment ends in a chunk (if above the LDS slots)
-  HIPC(hipMemcpyAsync(plan_words, b2 + o_nfix, sizeof plan_words, hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  P->n_fix[0] = plan_words[0]; P->n_fix[1] = plan_words[1];
-  P->windowed = plan_words[2] > (u32)PM_LDS_SLOTS;
-  if (c->tune.em_windowed == 1) P->windowed = true;
-  P->k = K; P->n_chunks = n_chunks; P->mflag = mflag; P->mpos = mpos; P->rpos = rpos;
-  P->roff = roff; P->coff = coff; P->rs = rs; P->cs = cs; P->nzpad = nzpad;
-  c->last_em_nnz_multi = NZ; c->last_em_nseg = n_chunks; c->last_em_necs = n_ecs; c->last_em_k = K;
-  c->last_em_grid = grid_for(n_chunks, PM_BLOCK / 64);
-  return 0;
-}
 
 // ---- component-local EM (kamd_em_local.h) -------------------------------------------------------------------------------------
 // One workgroup per group of connected components; the group's whole state lives in LDS for the rounds of a launch.  The plan
@@ -1079,12 +346,6 @@ constexpr int EML_MAX_ROUNDS = 64;   // rounds per launch (the per-group change 
 // j < width of the slice -- no row pointers, no cross-lane reduction except in the few slices that hold split segments (one
 // segmented DPP scan).  The lane that completes a segment finishes it at once (g = count / S for a row; next alpha, the
 // convergence test and a = alpha / eff for a transcript), so a round has two block barriers.
-struct EmSellDev {
-  const u32* row_base; const u32* tr_base; const u32* rslice_base; const u32* cslice_base; const u64* rell_base; const u64* cell_base;
-  const u32* rdesc; const u32* cdesc; const uint16_t* rell; const uint16_t* cell;
-  const u64* cw; const double* single; const double* eff;
-  const u32* grec;   // the six bases of group g and of g + 1 as ONE record of 16 words (k_sell_group_rec): a launch fetches it with one scalar load
-};
 constexpr int EMS_MAX_BLOCK = 1024;
 // sum over the lane's entries of one slice; e: the lane's first 64-bit word of four u16 indices (kamd_em_sell.h: word q of the lane at e + q * 64)
 // EXP != 0: timing experiments (KAMD_EM_EXP, results are garbage): 1 = gathers at conflict-free addresses (indices still loaded),
@@ -2349,7 +1610,6 @@ __global__ void k_sell_refresh(const u64* __restrict__ ec_off, const u32* __rest
 // bodies are the streamed form's (pm_wave_load / pm_wave_pass / pm_fix); only the loop control differs: no EmState, the round's
 // vectors are kernel arguments, and what changes from chunk to chunk sits in a descriptor in device memory so that the 64 rounds of
 // a chunk are ONE hipGraph replayed for every chunk (4 launches per round at 3.5 us of host time each would otherwise bind the host).
-struct GiDesc { int* hist; int stopped; int pad; };   // this chunk's per-round change counts (null: not wanted); the run stopped in the previous chunk
 // one launch in front of a chunk: where its change counts go, and the stop rule of EMAlgorithm::run (:202-205) on the counts of the PREVIOUS
 // chunk, evaluated ONCE here -- every kernel of the chunk then reads one word (a chunk queued behind the one the run stops in does nothing)
 __global__ void k_gi_set_desc(GiDesc* d, EmsPrev prev, int* hist) {
@@ -2468,18 +1728,6 @@ constexpr int GB_PF = 4;                                   // chunks of a wavefr
 constexpr int GB_K = 8, GB_CH = 64 * GB_K;                  // entries per lane and chunk (one 16-byte load), entries per chunk
 constexpr int GB_WAVES = 16, GB_THREADS = 64 * GB_WAVES;   // one workgroup per compute unit: 64 KB of block + 16 x 4 KB of piece sums
 constexpr uint16_t GB_END = 0x8000u, GB_PAD = (uint16_t)GB_B;   // entry = in-block index | GB_END on the last entry of a piece; padding reads the zero slot
-struct GbSide {
-  const uint16_t* stream;   // [n_chunks * GB_CH]; the chunks of a block are consecutive, a block starts on a chunk boundary
-  const u32* seg_base;      // [n_chunks] pieces that end in earlier chunks (= id of the chunk's first piece)
-  const u32* lane_word;     // [n_chunks * 64] as PmSide::lane_word
-  const u32* piece_slot;    // [n_pieces] where a piece's sum goes in `part`
-  double* part;             // [n_pieces]
-  const u32* slot_base;     // [n_seg + 1] the slots of a segment's pieces: slot_base[s] .. slot_base[s + 1]
-  const u32* wg_desc;       // [2 * n_wg] per workgroup: its work items wg_items[first .. end)
-  const u32* wg_items;      // [4 * n_items] block, first chunk, end chunk, rotation of the block's load: a workgroup loads the block, then its wavefronts take the chunks
-  u32 n_wg, n_chunks, n_pieces, n_seg, n_tgt;
-};
-struct GbArgs { GbSide rows, cols; const u64* cw; const double* single; const double* eff; u32 R, M; };
 template <int DIR>
 __global__ __launch_bounds__(GB_THREADS) void k_gb_pass(GbArgs A, const double* a_src, const GiDesc* desc) {
   extern __shared__ __attribute__((aligned(16))) double gb_lds[];
@@ -2809,26 +2057,6 @@ __global__ __launch_bounds__(BLOCK) void k_gb_piece_slot(const uint16_t* __restr
   for (int i = 0; i < GB_K; i++) if (stream[p0 + i] & GB_END) piece_slot[id++] = end_slot[p0 + i];
   if (lane == 0) seg_base[c] = (u32)seg_base64[c];
 }
-struct GbPlan { GbArgs args{}; bool valid = false; };
-struct GiantPart {
-  PmPlan plan;
-  double* G_al[2] = {nullptr, nullptr}; double* G_a[2] = {nullptr, nullptr};   // the ping-pong state of the chunks (chunk k: [k & 1] -> [(k + 1) & 1])
-  double* S_al[2] = {nullptr, nullptr}; double* S_a[2] = {nullptr, nullptr};   // what the rounds inside a chunk alternate between
-  double* ac = nullptr;
-  GiDesc* desc = nullptr;
-  hipStream_t stream = nullptr; hipEvent_t ev = nullptr;
-  hipGraph_t graph[2] = {nullptr, nullptr}; hipGraphExec_t gexec[2] = {nullptr, nullptr};
-  bool use_graph = true;
-  u64 nnz = 0, rows = 0;
-  GbPlan gb;   // the same rounds in 2-D blocks with the gathers out of LDS (gb.valid), three launches per round instead of k_gi_rows / k_gi_cols
-  void drop_graphs() {
-    for (int i = 0; i < 2; i++) {
-      if (gexec[i]) (void)hipGraphExecDestroy(gexec[i]);
-      if (graph[i]) (void)hipGraphDestroy(graph[i]);
-      gexec[i] = nullptr; graph[i] = nullptr;
-    }
-  }
-};
 // builds one direction of the blocked form from the streamed plan's segments (off, ids); 0 = ok, 1 = not applicable, < 0 = error
 int gb_setup_side(kamd_ctx* c, const u64* off, const u32* ids, u64 n_seg, u64 n_tgt, int dir, GbSide* out) {
   const int shift = dir == 0 ? GB_SHIFT_A : GB_SHIFT_G;
@@ -3043,30 +2271,6 @@ int gi_launch_chunk(GiantPart& G, int n, int clamp, int pin, int pout, int* d_h,
   HIPC(hipGetLastError());
   return 0;
 }
-}  // namespace
-namespace kamdi {
-struct SellCache {
-  bool valid = false;
-  const u64* d_ec_off = nullptr; const u32* d_ec_ids = nullptr; u64 n_ecs = 0, nnz = 0, T = 0, generation = 0;
-  int split_len = 0, group_div = 0, small_nnz = 0;
-  bool host_maps = false;   // P.tr_id / P.single_all were read back (the host-side scatter of several ranks needs them)
-  kamd_em_sell::Plan P;      // host part (tr_id, single_all, bases)
-  EmSellDev dev{};           // device part, in ctx->ems_plan
-  u32* row_final = nullptr; u32* mslot = nullptr; double* single_all = nullptr; double* d_eff = nullptr;   // in ctx->ems_maps
-  bool hybrid = false;       // G holds the streamed plan of the components beyond a workgroup's LDS; P / dev the others
-  GiantPart G;
-  // what a cached hybrid plan needs to take new counts (a bootstrap replicate): the split of the rows into the two sub-matrices (arrays in ctx->hy_sub)
-  struct HyKeep {
-    const u32* flag_s = nullptr; const u32* flag_g = nullptr; const u64* rpos_s = nullptr; const u64* rpos_g = nullptr;
-    const u64* off_s = nullptr; const u64* off_g = nullptr; const u32* ids_s = nullptr; const u32* ids_g = nullptr;
-    u32* cnt_s = nullptr; u32* cnt_g = nullptr; u32* wc_s = nullptr; u32* wc_g = nullptr;
-    u64 n_s = 0, n_g = 0; bool no_groups = false;
-  } hy;
-  int giant_nnz_t = 0, blocked_t = 0, hybrid_t = 0;   // tuning the cached plan was built under
-  ~SellCache() { G.drop_graphs(); }
-};
-}  // namespace kamdi
-namespace {
 
 // ---- the sliced-ELLPACK form: device plan + backend of kamd_em_local::run --------------------------------------------------
 __global__ void k_em_publish(EmsPrev prev);
@@ -3693,9 +2897,66 @@ int em_hybrid_refresh(kamd_ctx* c, SellCache& K, const u32* d_counts, const u32*
   HIPC(hipMemsetAsync(c->em_single.p, 0, T * sizeof(double), c->stream));
   hipLaunchKernelGGL(k_gi_refresh, dim3(grid_for(H.n_g, BLOCK)), dim3(BLOCK), 0, c->stream, H.off_g, H.ids_g, (const u32*)H.cnt_g, (const u32*)H.wc_g, H.n_g, G.plan.rpos,
                      const_cast<u64*>(A.cw), c->em_single.as<double>());
-  hipLaunchKernelGGL(k_pm_minit, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, G.plan.mflag, G.plan.mpos, (const u64*)nullptr, (const double*)c->em_single.as<double>(),
-                     (const double*)c->em_eff.as<double>(), (u64)A.M, (u64*)nullptr, const_cast<double*>(A.single), const_cast<double*>(A.eff), A.alpha0, A.alpha1, A.a0, A.a1, A.ac0, A.ac1);
+  pm_refresh_enqueue(c, G.plan, T);
   HIPC(hipGetLastError());
+  return 0;
+}
+// A new plan of this matrix into K: the hybrid first where the context's last matrix needed it, else the search for the group size, then the
+// hybrid if a component fits no group; with several ranks "this form does not apply" is agreed on by all of them.  own: the matrix is the
+// context's finalized one, whose plan is kept.  0 = K holds the plan, 1 = not applicable, < 0 = error
+int em_sell_choose_plan(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, const u32* d_counts, const u32* d_wcounts, u64 n_ecs, u64 nnz,
+                        const double* eff_lens, u64 T, bool multi, const EmPartition* part, bool own, SellCache& K) {
+  const auto plan_t0 = std::chrono::steady_clock::now();
+  K.valid = false; K.hybrid = false;
+  c->last_em_giant_nnz = 0; c->last_em_giant_rows = 0; c->last_em_giant_tr = 0; c->last_em_giant_chunks = 0; c->last_em_giant_pieces = 0;
+  // groups of nnz / (CUs x div) entries; a group must fit a workgroup's LDS (components are not split: if one does not fit, the
+  // cut is refined a few times; a single component beyond the CU's 160 KB sends the oversized components to the streamed kernels
+  // beside the groups -- the hybrid, em_hybrid_setup -- or, with several ranks, the whole matrix to the streamed form)
+  const u64 lds_budget = 160 * 1024 - 2048;
+  int prc = 1;
+  if (multi && n_ecs == 0) {   // a rank that owns no component still takes part in the collectives: an empty plan
+    K.P = kamd_em_sell::Plan{};
+    K.P.T = T; K.P.row_base.assign(1, 0); K.P.tr_base.assign(1, 0); K.P.single_all.assign(T, 0.0);
+    K.dev = EmSellDev{};
+    prc = 0;
+  } else {
+    // (several ranks: the rank that owns an oversized component runs the hybrid on its rows like one rank would; kamd_em_local::run drives it)
+    const bool may_hybrid = c->tune.em_hybrid != 2 && n_ecs > 0;
+    if (may_hybrid && c->em_prefer_hybrid) {   // the context's last matrix needed the hybrid (bootstrap replicates, the steps of a bench): start there
+      prc = em_hybrid_setup(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, K, true, multi);
+      if (prc < 0) return prc;
+      if (prc == 1) { K.hybrid = false; c->em_prefer_hybrid = false; }
+    }
+    if (prc == 1) {
+      CompStats cst{};
+      prc = em_sell_plan_search(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, c->n_cus, multi, K, &cst);
+      c->last_em_max_comp_nnz = cst.max_nnz;
+      if (prc == 1 && may_hybrid && cst.max_nnz > 0) {
+        prc = em_hybrid_setup(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, K, false, multi);
+        if (prc == 1) K.hybrid = false;
+        else if (prc == 0) c->em_prefer_hybrid = true;
+      }
+    }
+  }
+  if (prc < 0) return prc;
+  bool not_applicable = prc == 1 || (!multi && K.P.n_groups == 0 && !K.hybrid);
+  if (multi) {
+    int flag = not_applicable ? 1 : 0;
+    if (int rc = c->pt_hist.ensure(64, 0, c->stream)) return rc;
+    HIPC(hipMemcpyAsync(c->pt_hist.p, &flag, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    if (int rc = part->cb(part->user, (int32_t*)c->pt_hist.p, 1)) return kamd::fail(-103, "kamd_em_run_partitioned: the sum callback failed (" + std::to_string(rc) + ")");
+    HIPC(hipMemcpyAsync(&flag, c->pt_hist.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    not_applicable = flag != 0;
+  }
+  if (not_applicable) return 1;
+  c->last_em_plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - plan_t0).count();
+  if (own) {
+    K.giant_nnz_t = c->tune.em_giant_nnz; K.blocked_t = c->tune.em_blocked; K.hybrid_t = c->tune.em_hybrid;
+    K.valid = true; K.d_ec_off = d_ec_off; K.d_ec_ids = d_ec_ids; K.n_ecs = n_ecs; K.nnz = nnz; K.T = T; K.generation = c->ec_generation;
+    K.split_len = c->tune.em_split_len; K.group_div = c->tune.em_group_div; K.small_nnz = c->tune.em_small_nnz; K.host_maps = multi;
+  }
   return 0;
 }
 // part (several ranks, each with the rows of the components it owns): the per-round change counts of a chunk are summed over the
@@ -3733,57 +2994,7 @@ int em_sell_run_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, co
       HIPC(hipStreamSynchronize(c->stream));
     }
   } else {
-    const auto plan_t0 = std::chrono::steady_clock::now();
-    K.valid = false; K.hybrid = false;
-    c->last_em_giant_nnz = 0; c->last_em_giant_rows = 0; c->last_em_giant_tr = 0; c->last_em_giant_chunks = 0; c->last_em_giant_pieces = 0;
-    // groups of nnz / (CUs x div) entries; a group must fit a workgroup's LDS (components are not split: if one does not fit, the
-    // cut is refined a few times; a single component beyond the CU's 160 KB sends the oversized components to the streamed kernels
-    // beside the groups -- the hybrid, em_hybrid_setup -- or, with several ranks, the whole matrix to the streamed form)
-    const u64 lds_budget = 160 * 1024 - 2048;
-    int prc = 1;
-    if (multi && n_ecs == 0) {   // a rank that owns no component still takes part in the collectives: an empty plan
-      K.P = kamd_em_sell::Plan{};
-      K.P.T = T; K.P.row_base.assign(1, 0); K.P.tr_base.assign(1, 0); K.P.single_all.assign(T, 0.0);
-      K.dev = EmSellDev{};
-      prc = 0;
-    } else {
-      // (several ranks: the rank that owns an oversized component runs the hybrid on its rows like one rank would; kamd_em_local::run drives it)
-      const bool may_hybrid = c->tune.em_hybrid != 2 && n_ecs > 0;
-      if (may_hybrid && c->em_prefer_hybrid) {   // the context's last matrix needed the hybrid (bootstrap replicates, the steps of a bench): start there
-        prc = em_hybrid_setup(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, K, true, multi);
-        if (prc < 0) return prc;
-        if (prc == 1) { K.hybrid = false; c->em_prefer_hybrid = false; }
-      }
-      if (prc == 1) {
-        CompStats cst{};
-        prc = em_sell_plan_search(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, c->n_cus, multi, K, &cst);
-        c->last_em_max_comp_nnz = cst.max_nnz;
-        if (prc == 1 && may_hybrid && cst.max_nnz > 0) {
-          prc = em_hybrid_setup(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, lds_budget, K, false, multi);
-          if (prc == 1) K.hybrid = false;
-          else if (prc == 0) c->em_prefer_hybrid = true;
-        }
-      }
-    }
-    if (prc < 0) return prc;
-    bool not_applicable = prc == 1 || (!multi && K.P.n_groups == 0 && !K.hybrid);
-    if (multi) {
-      int flag = not_applicable ? 1 : 0;
-      if (int rc = c->pt_hist.ensure(64, 0, c->stream)) return rc;
-      HIPC(hipMemcpyAsync(c->pt_hist.p, &flag, sizeof(int), hipMemcpyHostToDevice, c->stream));
-      HIPC(hipStreamSynchronize(c->stream));
-      if (int rc = part->cb(part->user, (int32_t*)c->pt_hist.p, 1)) return kamd::fail(-103, "kamd_em_run_partitioned: the sum callback failed (" + std::to_string(rc) + ")");
-      HIPC(hipMemcpyAsync(&flag, c->pt_hist.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HIPC(hipStreamSynchronize(c->stream));
-      not_applicable = flag != 0;
-    }
-    if (not_applicable) return 1;
-    c->last_em_plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - plan_t0).count();
-    if (own) {
-      K.giant_nnz_t = c->tune.em_giant_nnz; K.blocked_t = c->tune.em_blocked; K.hybrid_t = c->tune.em_hybrid;
-      K.valid = true; K.d_ec_off = d_ec_off; K.d_ec_ids = d_ec_ids; K.n_ecs = n_ecs; K.nnz = nnz; K.T = T; K.generation = c->ec_generation;
-      K.split_len = c->tune.em_split_len; K.group_div = c->tune.em_group_div; K.small_nnz = c->tune.em_small_nnz; K.host_maps = multi;
-    }
+    if (const int prc = em_sell_choose_plan(c, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, nnz, eff_lens, T, multi, part, own, K)) return prc;
   }
   const kamd_em_sell::Plan& P = K.P;
   const int chunk = EML_MAX_ROUNDS;
@@ -3822,6 +3033,73 @@ int em_sell_run_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, co
   if (rounds) *rounds = r;
   return 0;
 }
+// Several ranks: connected components of the transcript/EC graph, then the rows of the components this rank owns as a compact CSR (in the
+// context's pt_* buffers).  In: the matrix; out: this rank's rows of it
+struct EmCsr { const uint64_t* off; const u32* ids; const u32* counts; const u32* wcounts; uint64_t n_ecs; };
+int em_local_rows(kamd_ctx* c, const EmPartition& part, u64 T, const uint64_t* d_ec_off, const u32* d_ec_ids, const u32* d_counts,
+                  const u32* d_wcounts, uint64_t n_ecs, EmCsr* local) {
+  if (int rc = c->pt_label.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->pt_hist.ensure(64, 0, c->stream)) return rc;
+  if (int rc = cc_labels(c, (const u64*)d_ec_off, d_ec_ids, n_ecs, T)) return rc;
+  for (DBuf* b : {&c->pt_flag, &c->pt_len}) if (int rc = b->ensure((n_ecs + 1) * sizeof(u32), 0, c->stream)) return rc;
+  for (DBuf* b : {&c->pt_rowpos, &c->pt_nnzpos}) if (int rc = b->ensure((n_ecs + 2) * sizeof(u64), 0, c->stream)) return rc;
+  hipLaunchKernelGGL(k_part_sizes, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids, n_ecs,
+                     c->pt_label.as<u32>(), part.rank, part.world, c->pt_flag.as<u32>(), c->pt_len.as<u32>());
+  if (int rc = exclusive_scan(c, c->pt_flag.as<u32>(), n_ecs, c->pt_rowpos.as<u64>(), c->pt_rowpos.as<u64>() + n_ecs)) return rc;
+  if (int rc = exclusive_scan(c, c->pt_len.as<u32>(), n_ecs, c->pt_nnzpos.as<u64>(), c->pt_nnzpos.as<u64>() + n_ecs)) return rc;
+  u64 n_local = 0, nnz_local = 0;
+  HIPC(hipMemcpyAsync(&n_local, c->pt_rowpos.as<u64>() + n_ecs, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipMemcpyAsync(&nnz_local, c->pt_nnzpos.as<u64>() + n_ecs, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  if (int rc = c->pt_off.ensure((n_local + 2) * sizeof(u64), 0, c->stream)) return rc;
+  if (int rc = c->pt_ids.ensure((nnz_local + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->pt_counts.ensure((n_local + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->pt_wcounts.ensure((n_local + 1) * sizeof(u32), 0, c->stream)) return rc;
+  hipLaunchKernelGGL(k_part_copy, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids, d_counts,
+                     d_wcounts, n_ecs, c->pt_flag.as<u32>(), c->pt_rowpos.as<u64>(), c->pt_nnzpos.as<u64>(), c->pt_off.as<u64>(),
+                     c->pt_ids.as<u32>(), c->pt_counts.as<u32>(), c->pt_wcounts.as<u32>());
+  HIPC(hipMemcpyAsync(c->pt_off.as<u64>() + n_local, &nnz_local, sizeof(u64), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));  // nnz_local is a stack variable
+  HIPC(hipGetLastError());
+  *local = EmCsr{c->pt_off.as<uint64_t>(), c->pt_ids.as<u32>(), c->pt_counts.as<u32>(), c->pt_wcounts.as<u32>(), n_local};
+  return 0;
+}
+// Set-up of the CSR form: the transposed (transcript-major) copy of the multi-transcript rows, the work list of k_em_final (*n_active
+// transcripts that occur in some EC), the columns cut into *n_seg segments.  Needs col_cnt / em_coloff / em_single of the caller
+// (k_em_prepare + scan) and a zeroed col_fill; col_cnt is written too: its third (T + 1)-word part takes the segment counts
+int em_csr_setup(kamd_ctx* c, const uint64_t* d_ec_off, const u32* d_ec_ids, u64 n_ecs, u64 nnz, u64 T, u32* col_cnt, u32* col_fill,
+                 u64* n_active_out, u64* n_seg_out) {
+  u64 n_active = 0, n_seg = 0;
+  if (n_ecs) hipLaunchKernelGGL(k_em_transpose, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids,
+                                (u64)n_ecs, c->em_coloff.as<u64>(), col_fill, c->em_colrow.as<u32>());
+  // work list of k_em_final: transcripts that occur in some EC
+  if (int rc = c->em_actflag.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->em_actpos.ensure((T + 2) * sizeof(u64), 0, c->stream)) return rc;
+  if (int rc = c->em_active.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
+  hipLaunchKernelGGL(k_em_active, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, col_cnt, c->em_single.as<double>(),
+                     c->em_actflag.as<u32>());
+  if (int rc = exclusive_scan(c, c->em_actflag.as<u32>(), T, c->em_actpos.as<u64>(), c->em_actpos.as<u64>() + T)) return rc;
+  hipLaunchKernelGGL(k_em_init, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, c->em_eff.as<double>(), c->em_actflag.as<u32>(),
+                     c->em_actpos.as<u64>(), c->em_alpha.as<double>(), c->em_next.as<double>(), c->em_a0.as<double>(),
+                     c->em_a1.as<double>(), c->em_active.as<u32>());
+  HIPC(hipMemcpyAsync(&n_active, c->em_actpos.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  // column segments
+  u32* nseg = col_cnt + 2 * (T + 1);
+  hipLaunchKernelGGL(k_em_nseg, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, col_cnt, T, nseg);
+  if (int rc = exclusive_scan(c, nseg, T, c->em_segoff.as<u64>(), c->em_segoff.as<u64>() + T)) return rc;
+  HIPC(hipMemcpyAsync(&n_seg, c->em_segoff.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  u64 nnz_multi = 0;
+  HIPC(hipMemcpy(&nnz_multi, c->em_coloff.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost));
+  c->last_em_nnz = nnz; c->last_em_nnz_multi = nnz_multi; c->last_em_nseg = n_seg; c->last_em_necs = n_ecs;
+  if (int rc = c->em_segt.ensure((n_seg + 1) * sizeof(u32), 0, c->stream)) return rc;
+  if (int rc = c->em_partial.ensure((n_seg + 1) * sizeof(double), 0, c->stream)) return rc;
+  hipLaunchKernelGGL(k_em_segsetup, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, c->em_coloff.as<u64>(), c->em_segoff.as<u64>(), T,
+                     c->em_segt.as<u32>());
+  HIPC(hipGetLastError());
+  *n_active_out = n_active; *n_seg_out = n_seg;
+  return 0;
+}
 int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids, const uint32_t* d_counts,
                 const uint32_t* d_weight_counts, uint64_t n_ecs, const double* eff_lens, uint64_t n_targets, uint32_t n_iter,
                 uint32_t min_rounds, double* alpha, double* alpha_before_zeroes, int32_t* rounds, const EmPartition& part) {
@@ -3838,36 +3116,9 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
   if (T == 0) return kamd::fail(-1, "kamd_em_run: no targets");
   const bool spec = part.world > 1;
   if (spec && n_ecs) {
-    // connected components of the transcript/EC graph, then the rows of the components this rank owns as a compact CSR
-    u64 nnz_all = 0;
-    HIPC(hipMemcpyAsync(&nnz_all, (const u64*)d_ec_off + n_ecs, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    if (int rc = c->pt_label.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
-    if (int rc = c->pt_hist.ensure(64, 0, c->stream)) return rc;
-    if (int rc = cc_labels(c, (const u64*)d_ec_off, d_ec_ids, (u64)n_ecs, T)) return rc;
-    for (DBuf* b : {&c->pt_flag, &c->pt_len}) if (int rc = b->ensure((n_ecs + 1) * sizeof(u32), 0, c->stream)) return rc;
-    for (DBuf* b : {&c->pt_rowpos, &c->pt_nnzpos}) if (int rc = b->ensure((n_ecs + 2) * sizeof(u64), 0, c->stream)) return rc;
-    hipLaunchKernelGGL(k_part_sizes, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids, (u64)n_ecs,
-                       c->pt_label.as<u32>(), part.rank, part.world, c->pt_flag.as<u32>(), c->pt_len.as<u32>());
-    if (int rc = exclusive_scan(c, c->pt_flag.as<u32>(), n_ecs, c->pt_rowpos.as<u64>(), c->pt_rowpos.as<u64>() + n_ecs)) return rc;
-    if (int rc = exclusive_scan(c, c->pt_len.as<u32>(), n_ecs, c->pt_nnzpos.as<u64>(), c->pt_nnzpos.as<u64>() + n_ecs)) return rc;
-    u64 n_local = 0, nnz_local = 0;
-    HIPC(hipMemcpyAsync(&n_local, c->pt_rowpos.as<u64>() + n_ecs, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipMemcpyAsync(&nnz_local, c->pt_nnzpos.as<u64>() + n_ecs, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    if (int rc = c->pt_off.ensure((n_local + 2) * sizeof(u64), 0, c->stream)) return rc;
-    if (int rc = c->pt_ids.ensure((nnz_local + 1) * sizeof(u32), 0, c->stream)) return rc;
-    if (int rc = c->pt_counts.ensure((n_local + 1) * sizeof(u32), 0, c->stream)) return rc;
-    if (int rc = c->pt_wcounts.ensure((n_local + 1) * sizeof(u32), 0, c->stream)) return rc;
-    hipLaunchKernelGGL(k_part_copy, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids, d_counts,
-                       d_wcounts, (u64)n_ecs, c->pt_flag.as<u32>(), c->pt_rowpos.as<u64>(), c->pt_nnzpos.as<u64>(), c->pt_off.as<u64>(),
-                       c->pt_ids.as<u32>(), c->pt_counts.as<u32>(), c->pt_wcounts.as<u32>());
-    HIPC(hipMemcpyAsync(c->pt_off.as<u64>() + n_local, &nnz_local, sizeof(u64), hipMemcpyHostToDevice, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));  // nnz_local is a stack variable
-    HIPC(hipGetLastError());
-    d_ec_off = c->pt_off.as<uint64_t>(); d_ec_ids = c->pt_ids.as<u32>(); d_counts = c->pt_counts.as<u32>(); d_wcounts = c->pt_wcounts.as<u32>();
-    n_ecs = n_local;
-    (void)nnz_all;
+    EmCsr local{};
+    if (int rc = em_local_rows(c, part, T, d_ec_off, d_ec_ids, d_counts, d_wcounts, n_ecs, &local)) return rc;
+    d_ec_off = local.off; d_ec_ids = local.ids; d_counts = local.counts; d_wcounts = local.wcounts; n_ecs = local.n_ecs;
   }
   u64 nnz = 0;
   if (n_ecs) {
@@ -3922,42 +3173,12 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
     }
   }
   u64 n_active = 0, n_seg = 0;
-  if (!streamed) {
-  if (n_ecs) hipLaunchKernelGGL(k_em_transpose, dim3(grid_for(n_ecs, BLOCK)), dim3(BLOCK), 0, c->stream, (const u64*)d_ec_off, d_ec_ids,
-                                (u64)n_ecs, c->em_coloff.as<u64>(), col_fill, c->em_colrow.as<u32>());
-  // work list of k_em_final: transcripts that occur in some EC
-  if (int rc = c->em_actflag.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
-  if (int rc = c->em_actpos.ensure((T + 2) * sizeof(u64), 0, c->stream)) return rc;
-  if (int rc = c->em_active.ensure((T + 1) * sizeof(u32), 0, c->stream)) return rc;
-  hipLaunchKernelGGL(k_em_active, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, col_cnt, c->em_single.as<double>(),
-                     c->em_actflag.as<u32>());
-  if (int rc = exclusive_scan(c, c->em_actflag.as<u32>(), T, c->em_actpos.as<u64>(), c->em_actpos.as<u64>() + T)) return rc;
-  hipLaunchKernelGGL(k_em_init, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, c->em_eff.as<double>(), c->em_actflag.as<u32>(),
-                     c->em_actpos.as<u64>(), c->em_alpha.as<double>(), c->em_next.as<double>(), c->em_a0.as<double>(),
-                     c->em_a1.as<double>(), c->em_active.as<u32>());
-  HIPC(hipMemcpyAsync(&n_active, c->em_actpos.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  // column segments
-  u32* nseg = col_cnt + 2 * (T + 1);
-  hipLaunchKernelGGL(k_em_nseg, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, col_cnt, T, nseg);
-  if (int rc = exclusive_scan(c, nseg, T, c->em_segoff.as<u64>(), c->em_segoff.as<u64>() + T)) return rc;
-  HIPC(hipMemcpyAsync(&n_seg, c->em_segoff.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
-  HIPC(hipStreamSynchronize(c->stream));
-  u64 nnz_multi = 0;
-  HIPC(hipMemcpy(&nnz_multi, c->em_coloff.as<u64>() + T, sizeof(u64), hipMemcpyDeviceToHost));
-  c->last_em_nnz = nnz; c->last_em_nnz_multi = nnz_multi; c->last_em_nseg = n_seg; c->last_em_necs = n_ecs;
-  if (int rc = c->em_segt.ensure((n_seg + 1) * sizeof(u32), 0, c->stream)) return rc;
-  if (int rc = c->em_partial.ensure((n_seg + 1) * sizeof(double), 0, c->stream)) return rc;
-  hipLaunchKernelGGL(k_em_segsetup, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, c->em_coloff.as<u64>(), c->em_segoff.as<u64>(), T,
-                     c->em_segt.as<u32>());
-  HIPC(hipGetLastError());
-  }  // !streamed
+  if (!streamed) if (int rc = em_csr_setup(c, d_ec_off, d_ec_ids, n_ecs, nnz, T, col_cnt, col_fill, &n_active, &n_seg)) return rc;
   const int chunk = 64;
-  int row_lanes = 4;
-  row_lanes = c->tune.em_row_lanes;
+  const int row_lanes = c->tune.em_row_lanes;
   const unsigned grid_rows = grid_for(std::max<u64>(n_ecs, 1) * row_lanes, BLOCK);
   const unsigned grid_seg = grid_for(std::max<u64>(n_seg, 1) * EM_SEG_LANES, BLOCK);
-  unsigned fin_cap = 1024;
-  fin_cap = (unsigned)c->tune.em_fin_blocks;
+  const unsigned fin_cap = (unsigned)c->tune.em_fin_blocks;
   const unsigned grid_fin = (unsigned)std::min<u64>(grid_for(std::max<u64>(n_active, 1) * EM_FIN_LANES, BLOCK), fin_cap);
   // The launch-bound inner loop is captured once as a hipGraph of `chunk` rounds (4 kernels each) on a private stream
   // and replayed until the device-side state says done; all loop state lives in device memory, so every replay is

@@ -23,6 +23,7 @@
  *       BUSProcessor::processBuffer, barcode / UMI / sequence of a technology  src/ProcessReads.cpp:1486-1627, 1739-1746 -> kamd_bus_split, kamd_bus_records
  *       (the technology table and ParseTechnology, src/main.cpp:1283-1408, 778-870 -> kamd_bus_layout_parse)
  *       `bustools sort | bustools count` between those records and quant-tcc (not part of the reference) -> kamd_bus_sort, kamd_bus_count
+ *       `bustools correct` in front of them (not part of the reference either) -> kamd_bus_whitelist_create, kamd_bus_correct
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -123,7 +124,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 10
+#define KAMD_ABI_VERSION 11
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -580,6 +581,49 @@ int kamd_bus_sort(kamd_ctx*, kamd_bus_record* d_rec /* in/out, [n] */, uint64_t 
                   int collapse, uint64_t* n_out /* host */, kamd_bus_sort_stats* out /* nullable */);
 int kamd_bus_count(kamd_ctx*, const kamd_bus_record* d_sorted, uint64_t n, int mode, uint64_t* d_barcodes /* [n] */, kamd_bus_entry* d_entries /* [n] */,
                    kamd_bus_record* d_multi /* [n] */, kamd_bus_count_stats* out /* nullable */);
+
+/* ---- barcode whitelists: what `bustools correct` does, on the device ----
+ * The step between kamd_bus_records and kamd_bus_sort.  A whitelist is a set W of distinct barcodes of one length L (1 .. 32 bases), each encoded
+ * as the records hold barcodes (A0 C1 G2 T3, first base most significant, 2 L bits, nothing above).  N(b) = the members of W that differ from b in
+ * exactly one of the L base positions.  Every record gets a status (kamd_buscorrect.h restates the rule):
+ *   KAMD_BUS_COR_EXACT          b in W: kept unchanged
+ *   KAMD_BUS_COR_CORRECTED      b not in W, |N(b)| = 1: kept, barcode replaced by that member; umi, ec, count, flags and pad stay as they are
+ *   KAMD_BUS_COR_AMBIGUOUS      b not in W, |N(b)| >= 2: dropped
+ *   KAMD_BUS_COR_UNCORRECTABLE  b not in W, |N(b)| = 0, or b has a bit set above bit 2 L - 1: dropped
+ * The survivors are written compact and in input order.  The rule is this project's, held to a restatement; nobody has compared it with bustools.
+ *
+ * kamd_bus_whitelist_parse: a text of `len` bytes, one barcode per line ("\n" or "\r\n", empty lines skipped, either letter case) -> its codes.
+ * out == NULL: only counts (*n, *bc_len).  Otherwise up to `cap` codes are written and more lines than cap are an error (*n still says how many).
+ * Errors (-1, text in err: nullable, err_cap bytes incl. the NUL) name the line: a letter that is not ACGT, a length that differs from the first
+ * line's, a length above 32, an empty list.  Duplicates are allowed.  Host only, no file I/O.
+ *
+ * kamd_bus_whitelist_create: uploads h_codes[0 .. n) (host) and builds the membership table on the device, on the context stream: buckets of 64
+ * bytes with 8 keys each, a key's home bucket a hash of the key, an overflowing bucket continued in the next (wrapping); n_buckets = the power of
+ * two >= n / 4, at least 1 (load <= 0.5).  Refused (-1): a code with a bit above 2 bc_len - 1, n == 0, bc_len outside 1 .. 32.  Duplicates are
+ * stored once.  stats (nullable): max_chain = the longest probe sequence of an insertion, in buckets; bytes = the table's.  A context holds any
+ * number of whitelists; kamd_ctx_destroy frees those not freed by kamd_bus_whitelist_free.
+ *
+ * kamd_bus_correct: d_in[0 .. n) -> d_out[0 .. *n_out) (device buffers of n records, 16-byte aligned, distinct; fewer than 2^32 - 1 records, n == 0
+ * is fine), d_status (nullable, device, uint8 [n]): every input record's status.  One thread per record tests the barcode; the records that miss
+ * go to a list and get one wavefront each, lane j testing neighbour j (position j / 3, base XOR (j % 3) + 1); count / scan / scatter compacts.
+ * On the context stream, one synchronisation at the end for the counters.  The output is the same bytes on every run.  Scratch, kept in the
+ * context: 13 bytes per record (status, miss list, the corrected barcode) and 4 bytes per 256 records.  stats (nullable): last_ms = the call,
+ * neigh_ms = the neighbour kernel's part of it, by HIP events.  Same guarantees as kamd_bus_sort: touches neither the EC state, the counts, the
+ * tuple table nor the fragment-length sample; errors as that call reports them. */
+#define KAMD_BUS_COR_EXACT         0
+#define KAMD_BUS_COR_CORRECTED     1
+#define KAMD_BUS_COR_AMBIGUOUS     2
+#define KAMD_BUS_COR_UNCORRECTABLE 3
+typedef struct kamd_bus_whitelist kamd_bus_whitelist;
+typedef struct { uint64_t n_in, n_distinct, n_buckets, bytes; uint32_t max_chain; int32_t bc_len; float last_ms; } kamd_bus_whitelist_stats;
+typedef struct { uint64_t n_in, n_exact, n_corrected, n_ambiguous, n_uncorrectable, n_out; float last_ms, neigh_ms; } kamd_bus_correct_stats;
+int kamd_bus_whitelist_parse(const char* text, size_t len, uint64_t* out /* nullable, [cap] */, uint64_t cap, uint64_t* n, int32_t* bc_len, char* err,
+                             size_t err_cap);
+int kamd_bus_whitelist_create(kamd_ctx*, const uint64_t* h_codes, uint64_t n, int32_t bc_len, kamd_bus_whitelist** out,
+                              kamd_bus_whitelist_stats* stats /* nullable */);
+int kamd_bus_whitelist_free(kamd_ctx*, kamd_bus_whitelist*);
+int kamd_bus_correct(kamd_ctx*, const kamd_bus_whitelist*, const kamd_bus_record* d_in, uint64_t n, kamd_bus_record* d_out /* [n] */,
+                     uint8_t* d_status /* nullable, [n] */, uint64_t* n_out /* host */, kamd_bus_correct_stats* stats /* nullable */);
 
 /* ---- S3: EM ---- */
 /* Runs EMAlgorithm(counts, ...).run(n_iter, min_rounds) (src/EMAlgorithm.h:26-48,95-223) on the finalized EC result

@@ -63,7 +63,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 10   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 11   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -156,6 +156,34 @@ class _BusCountStats(C.Structure):
     """kamd_bus_count_stats"""
     _fields_ = [("n_records", C.c_uint64), ("n_barcodes", C.c_uint64), ("n_entries", C.c_uint64), ("n_umis", C.c_uint64), ("n_multi_groups", C.c_uint64),
                 ("n_multi_records", C.c_uint64), ("last_ms", C.c_float)]
+
+
+class _BusWhitelistStats(C.Structure):
+    """kamd_bus_whitelist_stats"""
+    _fields_ = [("n_in", C.c_uint64), ("n_distinct", C.c_uint64), ("n_buckets", C.c_uint64), ("bytes", C.c_uint64), ("max_chain", C.c_uint32), ("bc_len", C.c_int32),
+                ("last_ms", C.c_float)]
+
+
+class _BusCorrectStats(C.Structure):
+    """kamd_bus_correct_stats"""
+    _fields_ = [("n_in", C.c_uint64), ("n_exact", C.c_uint64), ("n_corrected", C.c_uint64), ("n_ambiguous", C.c_uint64), ("n_uncorrectable", C.c_uint64),
+                ("n_out", C.c_uint64), ("last_ms", C.c_float), ("neigh_ms", C.c_float)]
+
+
+BUS_COR_EXACT, BUS_COR_CORRECTED, BUS_COR_AMBIGUOUS, BUS_COR_UNCORRECTABLE = 0, 1, 2, 3   # KAMD_BUS_COR_*
+
+
+class BusWhitelist:
+    """a whitelist of a Context (kamd_bus_whitelist): the handle Context.bus_correct takes, the barcode length and what kamd_bus_whitelist_create
+    reported (n_in, n_distinct, n_buckets, max_chain, bytes, ms).  Context.close frees it; free() does so earlier."""
+
+    def __init__(self, ctx, handle, stats):
+        self._ctx, self._h, self.stats, self.bc_len = ctx, handle, stats, stats["bc_len"]
+
+    def free(self):
+        if self._h is not None and self._ctx._h is not None:
+            _check(load_library().kamd_bus_whitelist_free(self._ctx._h, self._h), "kamd_bus_whitelist_free")
+        self._h = None
 
 
 class BgzfMember(C.Structure):
@@ -269,6 +297,10 @@ _SYMBOLS = {
     "kamd_bus_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64)]),
     "kamd_bus_sort": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.POINTER(_BusSortStats)]),
     "kamd_bus_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(_BusCountStats)]),
+    "kamd_bus_whitelist_parse": (C.c_int, [C.c_char_p, C.c_size_t, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.c_char_p, C.c_size_t]),
+    "kamd_bus_whitelist_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(_BusWhitelistStats)]),
+    "kamd_bus_whitelist_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kamd_bus_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(_BusCorrectStats)]),
     "kamd_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "kamd_em_run_partitioned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
@@ -355,6 +387,33 @@ def bus_records_numpy(records) -> np.ndarray:
 def bus_entries_numpy(entries) -> np.ndarray:
     """the int32 [n, 3] tensor of Context.bus_count -> a host array of BUS_ENTRY_DTYPE"""
     return np.ascontiguousarray(entries.cpu().numpy()).reshape(-1).view(BUS_ENTRY_DTYPE)
+
+
+def bus_whitelist_parse(text: bytes):
+    """kamd_bus_whitelist_parse: the bytes of a whitelist file (one barcode per line) -> (codes uint64 [n], barcode length).  Raises KallistoAmdError
+    with the parser's text, which names the line."""
+    lib = load_library()
+    text = bytes(text)
+    n, L, err = C.c_uint64(0), C.c_int32(0), C.create_string_buffer(256)
+    if lib.kamd_bus_whitelist_parse(text, len(text), None, 0, C.byref(n), C.byref(L), err, len(err)) != 0:
+        raise KallistoAmdError(err.value.decode(errors="replace"))
+    codes = np.zeros(int(n.value), np.uint64)
+    if lib.kamd_bus_whitelist_parse(text, len(text), codes.ctypes.data, len(codes), C.byref(n), C.byref(L), err, len(err)) != 0:
+        raise KallistoAmdError(err.value.decode(errors="replace"))
+    return codes, int(L.value)
+
+
+def bus_whitelist_read(path: str):
+    """a whitelist file, plain text or gzip (told by its first bytes) -> (codes uint64 [n], barcode length); the text goes through the C parser"""
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:2] == b"\x1f\x8b":
+        import gzip
+        data = gzip.decompress(data)
+    try:
+        return bus_whitelist_parse(data)
+    except KallistoAmdError as e:
+        raise KallistoAmdError(f"{path}: {e}") from None
 
 
 def packed_record_words(max_len: int) -> int:
@@ -697,6 +756,43 @@ class Context:
         stats = {"n_records": int(st.n_records), "n_barcodes": int(st.n_barcodes), "n_entries": int(st.n_entries), "n_umis": int(st.n_umis),
                  "n_multi_groups": int(st.n_multi_groups), "n_multi_records": int(st.n_multi_records), "ms": float(st.last_ms)}
         return {"barcodes": barcodes[:stats["n_barcodes"]], "entries": entries[:stats["n_entries"]], "multi": multi[:stats["n_multi_records"]], "stats": stats}
+
+    # ---- barcode whitelists (bustools correct) ----
+    def bus_whitelist(self, codes_or_path, bc_len: int | None = None) -> BusWhitelist:
+        """kamd_bus_whitelist_create: a whitelist file (a path: bus_whitelist_read) or an array of codes with their barcode length -> a BusWhitelist
+        whose membership table lies on the device.  Duplicates are stored once; a code with a bit above 2 * bc_len raises."""
+        if isinstance(codes_or_path, (str, os.PathLike)):
+            codes, bc_len = bus_whitelist_read(os.fspath(codes_or_path))
+        else:
+            if bc_len is None:
+                raise KallistoAmdError("bus_whitelist: an array of codes needs its barcode length")
+            codes = np.ascontiguousarray(codes_or_path, np.uint64)
+        h, st = C.c_void_p(None), _BusWhitelistStats()
+        _check(load_library().kamd_bus_whitelist_create(self._h, codes.ctypes.data if len(codes) else None, len(codes), int(bc_len), C.byref(h), C.byref(st)),
+               "kamd_bus_whitelist_create")
+        return BusWhitelist(self, h, {"n_in": int(st.n_in), "n_distinct": int(st.n_distinct), "n_buckets": int(st.n_buckets), "max_chain": int(st.max_chain),
+                                      "bytes": int(st.bytes), "bc_len": int(st.bc_len), "ms": float(st.last_ms)})
+
+    def bus_correct(self, wl: BusWhitelist, records, want_status: bool = False):
+        """kamd_bus_correct: the int64 device tensor [n, 4] of BUS records (Context.bus_records) against a whitelist -> (the records that are on it or
+        one substitution away from exactly one member, the barcode of the latter replaced, compact and in input order: a new tensor [n_out, 4]; stats
+        dict: n_in, n_exact, n_corrected, n_ambiguous, n_uncorrectable, n_out, ms, neigh_ms[; the uint8 status of every input record, BUS_COR_*])."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        n = int(records.shape[0])
+        if n and not records.is_contiguous():
+            raise KallistoAmdError("bus_correct: the records must be a contiguous int64 [n, 4] tensor")
+        if wl._h is None or wl._ctx is not self:
+            raise KallistoAmdError("bus_correct: not a (live) whitelist of this context")
+        out = torch.empty((max(n, 1), 4), dtype=torch.int64, device=dev)
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if want_status else None
+        n_out, st = C.c_uint64(0), _BusCorrectStats()
+        _check(load_library().kamd_bus_correct(self._h, wl._h, records.data_ptr() if n else None, n, out.data_ptr(), status.data_ptr() if want_status else None,
+                                               C.byref(n_out), C.byref(st)), "kamd_bus_correct")
+        stats = {"n_in": int(st.n_in), "n_exact": int(st.n_exact), "n_corrected": int(st.n_corrected), "n_ambiguous": int(st.n_ambiguous),
+                 "n_uncorrectable": int(st.n_uncorrectable), "n_out": int(st.n_out), "ms": float(st.last_ms), "neigh_ms": float(st.neigh_ms)}
+        res = (out[:int(n_out.value)], stats)
+        return res + (status[:n],) if want_status else res
 
     # ---- translated search (bus --aa) ----
     def cfc_frames(self, words, lens, n_reads: int, max_len: int):

@@ -1,11 +1,11 @@
 """`kallisto bus -x <technology>` over the library: a small Python driver that writes a `kallisto bus` output directory for a barcode / UMI technology.
 
-    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] [--count] files...
+    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] [--count] [-w WHITELIST] files...
 
 TECH is a technology name (10XV3, SURECELL, INDROPSV2, VASA-SEQ, ...) or a custom "bc:umi:seq" string (BusLayout.parse); the files come in sets of the
 technology's file count, plain or gzip.  Per batch of UNIT_RECORDS read sets the driver runs
 
-    reset -> bus_split -> pseudoalign -> finalize -> read_ecs -> bus_records -> bus_sort (the batch's classes as its map) -> download of the batch's classes
+    reset -> bus_split -> pseudoalign -> finalize -> read_ecs -> bus_records -> [bus_correct] -> bus_sort (the batch's classes as its map) -> download of the batch's classes
 
 Class ids are batch-local; they are mapped to the ids of matrix.ec by transcript set, batch by batch in order of first appearance (the new sets of a batch in ascending order), so the input is read once and
 nothing of a batch is kept but its records.  The records stay on the device: every batch's are sorted and collapsed there (kamd_bus_sort), the
@@ -20,6 +20,13 @@ is counted on the device (kamd_bus_count: distinct UMIs per (barcode, class), or
 several classes is resolved here as bustools does: the transcript sets of its classes are intersected, an empty intersection drops the UMI,
 otherwise it counts 1 for the class of the intersection, which is appended to matrix.ec when it is new.  `kallisto_amd_quant quant-tcc -e
 counts/output.ec.txt counts/output.mtx` takes the result.
+
+-w / --whitelist FILE: what `bustools correct` does between the records and their sort.  FILE lists the technology's barcodes, one per line, plain
+or gzip.  Every batch's records go through kamd_bus_correct: a record whose barcode is on the list is kept, one whose barcode is one substitution
+away from exactly one listed barcode takes that barcode, every other record is dropped.  output.bus and --count then hold listed barcodes only.
+The four counters (n_exact, n_corrected, n_ambiguous, n_uncorrectable) go into out/correct.json and into the dict run() returns; run_info.json keeps
+the reference's keys and meanings, n_pseudoaligned is counted before the correction.  Refused where the layout has no barcode, where a barcode part
+is open-ended, and where the barcode's length differs from the list's.
 
 This is a driver for moderate inputs: the collapsed records of the whole run are held in device memory and the FASTQ text is read through Python.  It is not the
 streaming C++ front-end (`kallisto_amd_quant bus` takes `-x bulk` only): the product is the C ABI, which a front-end that parses `-x` itself binds.
@@ -82,8 +89,9 @@ def _pack_unit(ctx, texts, n_records, n_files):
 
 
 def run(technology, index_path, out_dir, files, strand=None, no_jump=False, union=False, per_read=False, unit_records=UNIT_RECORDS, device=0, call="", count=False,
-        merge_records=MERGE_RECORDS):
+        merge_records=MERGE_RECORDS, whitelist=None):
     layout, default_strand = A.BusLayout.parse(technology)
+    wl_codes = _read_whitelist(whitelist, layout, technology) if whitelist else None
     if strand is None:
         strand = default_strand
     if len(files) == 0 or len(files) % layout.n_files:
@@ -96,6 +104,8 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
     ec_of, ec_sets = {}, []          # transcript set -> id of matrix.ec, in order of first appearance
     chunks, since_merge = [], 0      # sorted device chunks of records, classes already global; records that came in since the last merge
     torch = ctx.torch
+    wl = ctx.bus_whitelist(wl_codes[0], wl_codes[1]) if wl_codes else None
+    corrected = dict.fromkeys(CORRECT_KEYS, 0)
 
     def merge():
         """the chunks held -> one sorted (and, unless per_read, collapsed) chunk"""
@@ -137,7 +147,11 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
                     row_to_ec[r] = ec_of[key]
                     if len(key) == 1:
                         n_unique += int(ecs.counts[r])
-                n_pseudoaligned += int(d_rec.shape[0])
+                n_pseudoaligned += int(d_rec.shape[0])   # (before the correction: what the reference counts)
+                if wl is not None:
+                    d_rec, cst = ctx.bus_correct(wl, d_rec)
+                    for k in CORRECT_KEYS:
+                        corrected[k] += cst[k]
                 if d_rec.shape[0] == 0:
                     continue
                 srt, _ = ctx.bus_sort(d_rec, torch.from_numpy(row_to_ec).to(d_rec.device), collapse=not per_read)
@@ -172,8 +186,30 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
     with open(os.path.join(out_dir, "run_info.json"), "w") as f:
         json.dump(info, f, indent=1)
         f.write("\n")
+    if wl is not None:
+        with open(os.path.join(out_dir, "correct.json"), "w") as f:
+            json.dump(corrected, f, indent=1)
+            f.write("\n")
+        counted = dict(counted, **corrected)
     info = dict(info, **counted)   # (run_info.json keeps the reference's keys)
     return info
+
+
+CORRECT_KEYS = ("n_exact", "n_corrected", "n_ambiguous", "n_uncorrectable")
+
+
+def _read_whitelist(path, layout, technology):
+    """the whitelist file of -w -> (codes, barcode length), or the reason why this technology's records cannot be corrected against it"""
+    parts = layout.parts("bc")
+    if parts[0][0] < 0:
+        raise A.KallistoAmdError(f"-w/--whitelist: technology {technology} has no barcode")
+    if any(stop == 0 for _, _, stop in parts):
+        raise A.KallistoAmdError(f"-w/--whitelist: a barcode part of technology {technology} is open-ended: its barcodes have no fixed length")
+    tech_len = sum(stop - start for _, start, stop in parts)
+    codes, wl_len = A.bus_whitelist_read(path)
+    if wl_len != tech_len:
+        raise A.KallistoAmdError(f"barcode length of whitelist ({wl_len}) differs from the technology's ({tech_len})")
+    return codes, wl_len
 
 
 def count_mode(layout):
@@ -241,12 +277,13 @@ def main(argv=None):
     ap.add_argument("--union", action="store_true")
     ap.add_argument("--bus-per-read", action="store_true")
     ap.add_argument("--count", action="store_true", help="also write the barcodes x classes matrix of the records into <output-dir>/counts")
+    ap.add_argument("-w", "--whitelist", metavar="FILE", help="correct the records' barcodes against this list (one barcode per line, plain or gzip): what `bustools correct` does")
     ap.add_argument("--unit-records", type=int, default=UNIT_RECORDS, help=argparse.SUPPRESS)
     ap.add_argument("--merge-records", type=int, default=MERGE_RECORDS, help=argparse.SUPPRESS)
     ap.add_argument("files", nargs="+")
     a = ap.parse_args(argv)
     try:
-        info = run(a.technology, a.index, a.output_dir, a.files, a.strand, a.no_jump, a.union, a.bus_per_read, a.unit_records, count=a.count, merge_records=a.merge_records,
+        info = run(a.technology, a.index, a.output_dir, a.files, a.strand, a.no_jump, a.union, a.bus_per_read, a.unit_records, count=a.count, merge_records=a.merge_records, whitelist=a.whitelist,
                    call="python -m kallisto_amd.bus_sc " + " ".join(sys.argv[1:] if argv is None else argv))
     except A.KallistoAmdError as e:
         print("Error:", e, file=sys.stderr)

@@ -1,5 +1,5 @@
 // kamd_bus.cpp -- host side of the barcode / UMI technologies: technology name or "bc:umi:seq" string -> kamd_bus_layout (kamd_bus_layout_parse),
-// the check of a layout (kamd::bus_layout_check) and kamd_bus_seq_max_len.  No GPU code, no dependency on the rest of the library: tests/emu_bustag
+// the check of a layout (kamd::bus_layout_check), kamd_bus_seq_max_len, and the text of a barcode whitelist -> codes (kamd_bus_whitelist_parse).  No GPU code, no dependency on the rest of the library: tests/emu_bustag
 // compiles this file for the CPU as it is.
 //
 // The reference keeps one branch per technology name (src/main.cpp:1283-1408) and a parser for custom strings (ParseTechnology, :778-870).  Here a name is
@@ -195,4 +195,54 @@ extern "C" int32_t kamd_bus_seq_max_len(const kamd_bus_layout* L, int32_t max_le
   const int32_t end = (L->seq.stop && L->seq.stop < max_len) ? L->seq.stop : max_len;
   const int32_t n = end - L->seq.start;
   return n > 1 ? n : 1;
+}
+
+// ---- barcode whitelists: the text of a whitelist file -> codes (kamd_bus_whitelist_parse).  The caller reads the file; lines are counted from 1,
+// empty ones included, so that an error names the line an editor shows ----
+extern "C" int kamd_bus_whitelist_parse(const char* text, size_t len, uint64_t* out, uint64_t cap, uint64_t* n, int32_t* bc_len, char* err, size_t err_cap) {
+  if (err && err_cap) err[0] = 0;
+  if (n) *n = 0;
+  if (bc_len) *bc_len = 0;
+  if ((!text && len) || !n || !bc_len) return set_err(err, err_cap, "kamd_bus_whitelist_parse: null argument");
+  uint64_t count = 0, line = 0;
+  size_t L = 0;
+  for (size_t pos = 0; pos < len;) {
+    size_t end = pos;
+    while (end < len && text[end] != '\n') ++end;
+    size_t stop = end;
+    if (stop > pos && text[stop - 1] == '\r') --stop;
+    ++line;
+    const size_t l = stop - pos;
+    if (l) {
+      if (l > 32) return set_err(err, err_cap, "whitelist line " + std::to_string(line) + ": " + std::to_string(l) + " bases, a barcode holds at most 32");
+      if (count == 0) L = l;
+      else if (l != L)
+        return set_err(err, err_cap, "whitelist line " + std::to_string(line) + ": " + std::to_string(l) + " bases, the first barcode has " + std::to_string(L));
+      uint64_t code = 0;
+      for (size_t i = pos; i < stop; i++) {
+        int b;
+        switch (text[i]) {
+          case 'A': case 'a': b = 0; break;
+          case 'C': case 'c': b = 1; break;
+          case 'G': case 'g': b = 2; break;
+          case 'T': case 't': b = 3; break;
+          default: {
+            char shown[8];
+            const unsigned char ch = (unsigned char)text[i];
+            if (ch >= 0x21 && ch < 0x7F) snprintf(shown, sizeof shown, "'%c'", (char)ch); else snprintf(shown, sizeof shown, "0x%02X", ch);
+            return set_err(err, err_cap, "whitelist line " + std::to_string(line) + ": " + shown + " at base " + std::to_string(i - pos + 1) + " is not one of ACGT");
+          }
+        }
+        code = (code << 2) | (uint64_t)b;
+      }
+      if (out && count < cap) out[count] = code;
+      ++count;
+    }
+    pos = end + 1;
+  }
+  *n = count;
+  *bc_len = (int32_t)L;
+  if (count == 0) return set_err(err, err_cap, "whitelist: no barcode in it");
+  if (out && count > cap) return set_err(err, err_cap, "whitelist: " + std::to_string(count) + " barcodes, the output holds " + std::to_string(cap));
+  return 0;
 }

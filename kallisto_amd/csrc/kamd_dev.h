@@ -16,7 +16,9 @@
 //   kamd_bus.hip     barcode / UMI technologies: tags, drops and the cut sequence of every item, compacted (kamd_bus_split), and the 32-byte BUS records
 //                    of a cut batch (kamd_bus_records); per-item rules in kamd_bustag.h, the layout parser in kamd_bus.cpp
 //   kamd_bussort.hip BUS records -> cells x classes: the stable LSD sort with collapse (kamd_bus_sort) and rows / distinct UMIs per class / multi-class
-//                    groups (kamd_bus_count); per-record rules in kamd_bussort.h, the scan both bus units share in kamd_bus_scan.h
+//                    groups (kamd_bus_count); per-record rules in kamd_bussort.h, the scan the bus units share in kamd_bus_scan.h
+//   kamd_buscorrect.hip barcode whitelists: the membership table built on the device (kamd_bus_whitelist_create) and the correction of a batch's
+//                    records against it (kamd_bus_correct); the table's rules and the rule of the correction in kamd_buscorrect.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -362,6 +364,11 @@ struct kamd_ctx {
   // BUS records -> cells x classes (kamd_bussort.hip): the second buffer of the sort (n records), the [digit][block] histograms and their 256 totals,
   // the 64-bit sums of the collapse, the counters of a call; kamd_bus_count's unit records (its second sort's input), group starts, per-record marks
   DBuf bsort_b, bsort_hist, bsort_tot, bsort_sum, bsort_ctr, bcnt_units, bcnt_gstart, bcnt_mark, bcnt_blk;
+  // barcode whitelists (kamd_buscorrect.hip): the whitelists of this context (freed with it); of a kamd_bus_correct call the status of every record
+  // (where the caller passes none), the indices of the records that miss the table, the barcode a corrected record takes, the counters
+  std::vector<struct kamd_bus_whitelist*> whitelists;
+  DBuf bcor_status, bcor_miss, bcor_fix, bcor_ctr;
+  hipEvent_t bcor_ev[2] = {nullptr, nullptr};
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 
@@ -372,6 +379,8 @@ int push_state(kamd_ctx* c);
 void apply_quant_opts(kamd_ctx* c, const kamd_quant_opts* o);
 void apply_tuning(kamd_ctx* c);
 void comm_detach_all(kamd_ctx* c);
+// kamd_buscorrect.hip
+void whitelists_free_all(kamd_ctx* c);
 // kamd_ixbuild.hip
 int index_build_device(kamd_ctx* c, const kamd_index* hix, const kamd_index_view& v, DevIndex* d, kamd_table_info* info);
 // kamd_ec.hip

@@ -124,7 +124,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 11
+#define KAMD_ABI_VERSION 12
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -213,6 +213,11 @@ typedef struct {
   int32_t em_blocked;          /* hybrid: 1 (default) = the oversized components are iterated in 2-D blocks -- the gathered vector's block in LDS, 16-bit in-block
                                   indices, partial sums per (segment, block) combined in a fixed order: three launches per round (k_gb_pass<0>, k_gb_pass<1>,
                                   k_gb_finish); 2 = the streamed kernels k_gi_rows / k_gi_cols gather through the vector memory pipeline (round 5) */
+  int32_t fld_list_cap;        /* test hook, fragment-length sample: entries of the per-item class list in the first k_fld launch of a prefix (1..64;
+                                  default 64).  An item with more distinct classes is re-run with the large list and the prefix's sample is then
+                                  taken on the host -- a path real reads hardly ever reach.  The scratch stays sized for 64 entries */
+  int32_t fld_first_chunk;     /* test hook, fragment-length sample: items of the first prefix kamd_fld_prefetch / kamd_fld_from_batch look at
+                                  (64..1048576; default 1048576); later prefixes are sized from the rate of qualifying pairs seen so far */
 } kamd_tuning;
 int kamd_ctx_tune(kamd_ctx*, const kamd_tuning*);
 int kamd_ctx_get_tuning(const kamd_ctx*, kamd_tuning* out);
@@ -368,6 +373,10 @@ typedef struct {
                                       straight-line kernel */
   uint64_t last_em_giant_pieces;   /* hybrid, blocked form: partial sums per round over both directions (segments cut at block and chunk boundaries); 0 = the
                                       streamed kernels ran */
+  uint32_t last_fld_chunks;        /* the last kamd_fld_from_batch call: prefixes of the batch it processed (0: the sample was full already, or no items), */
+  uint64_t last_fld_candidates;    /* pairs k_fld_first passed on to k_fld, summed over those prefixes, */
+  uint64_t last_fld_list_overflows; /* of them: pairs whose class list overflowed the first k_fld launch (such a prefix's sample is taken on the host), */
+  int32_t last_fld_prefetched;     /* 1 = the first prefix's result came from kamd_fld_prefetch's launch behind kernel A */
 } kamd_profile;
 int kamd_profile_get(kamd_ctx*, kamd_profile* out);
 

@@ -9,6 +9,7 @@ void tuning_defaults(kamd_tuning* t) {
   t->em_form = 3; t->em_local_block = 1024; t->em_group_div = -1; t->em_split_len = 16; t->em_small_nnz = -1; t->em_entries_per_lane = -1; t->em_windowed = 2; t->em_graph = 1; t->em_row_lanes = 4;
   t->em_fin_blocks = 1024; t->dedup_form = 2; t->align_chunks = -1; t->em_reg_slices = 1;
   t->em_hybrid = 1; t->overflow_second_pass = 1; t->em_giant_nnz = -1; t->em_blocked = 1;
+  t->fld_list_cap = 64; t->fld_first_chunk = 1048576;
 }
 // 0 = keep; values outside a field's range are ignored
 void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
@@ -34,6 +35,8 @@ void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
   if (n.overflow_second_pass >= 1 && n.overflow_second_pass <= 3) t->overflow_second_pass = n.overflow_second_pass;
   if (n.em_blocked == 1 || n.em_blocked == 2) t->em_blocked = n.em_blocked;
   if (n.em_giant_nnz != 0) t->em_giant_nnz = n.em_giant_nnz < 0 ? -1 : std::max(n.em_giant_nnz, 8);
+  if (n.fld_list_cap >= 1 && n.fld_list_cap <= 64) t->fld_list_cap = n.fld_list_cap;
+  if (n.fld_first_chunk >= 64 && n.fld_first_chunk <= 1048576) t->fld_first_chunk = n.fld_first_chunk;
 }
 // experiments: the same knobs from ONE environment variable, read once when a context is created --
 //   KAMD_TUNE="em_form=streamed,em_graph=0,items_per_wave=512"   (field names of kamd_tuning; on/off fields take 1 / 0; em_form also by name)
@@ -50,7 +53,8 @@ void tuning_from_env(kamd_tuning* t) {
     {"em_fin_blocks", &kamd_tuning::em_fin_blocks, false}, {"em_local_block", &kamd_tuning::em_local_block, false}, {"em_group_div", &kamd_tuning::em_group_div, false},
     {"em_split_len", &kamd_tuning::em_split_len, false}, {"dedup_form", &kamd_tuning::dedup_form, false}, {"align_chunks", &kamd_tuning::align_chunks, false},
     {"em_small_nnz", &kamd_tuning::em_small_nnz, false}, {"em_reg_slices", &kamd_tuning::em_reg_slices, true}, {"em_hybrid", &kamd_tuning::em_hybrid, true},
-    {"overflow_second_pass", &kamd_tuning::overflow_second_pass, false}, {"em_giant_nnz", &kamd_tuning::em_giant_nnz, false}, {"em_blocked", &kamd_tuning::em_blocked, true}};
+    {"overflow_second_pass", &kamd_tuning::overflow_second_pass, false}, {"em_giant_nnz", &kamd_tuning::em_giant_nnz, false}, {"em_blocked", &kamd_tuning::em_blocked, true},
+    {"fld_list_cap", &kamd_tuning::fld_list_cap, false}, {"fld_first_chunk", &kamd_tuning::fld_first_chunk, false}};
   std::string all(e);
   for (size_t pos = 0; pos < all.size();) {
     size_t end = all.find(',', pos);
@@ -405,6 +409,8 @@ extern "C" int kamd_profile_get(kamd_ctx* c, kamd_profile* p) {
   p->n_overflow_items = c->overflow_total; p->overflow_ms = c->overflow_ms;
   p->n_overflow_second_pass = c->overflow_second_total;
   p->last_merge_ms = c->last_merge_ms; p->em_collective_ms = c->em_coll_ms; p->em_collectives = c->em_coll_n;
+  p->last_fld_chunks = c->last_fld_chunks; p->last_fld_candidates = c->last_fld_candidates; p->last_fld_list_overflows = c->last_fld_list_overflows;
+  p->last_fld_prefetched = c->last_fld_prefetched;
   return 0;
 }
 

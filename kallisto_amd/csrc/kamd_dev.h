@@ -297,11 +297,12 @@ struct kamd_ctx {
   void* fld_host = nullptr; u64 fld_host_cap = 0;   // pinned staging of kamd_fld_from_batch
   // kamd_fld_prefetch: the first prefix of a batch, launched on a side stream so that it overlaps kernel A
   hipStream_t fld_stream = nullptr; hipEvent_t fld_ev = nullptr, fld_ev_in = nullptr;
-  struct { const uint32_t* w = nullptr; const uint16_t* l = nullptr; u64 n = 0; int32_t max_len = 0, strand = 0, so = 0; bool valid = false; } fld_pending;
+  struct { const uint32_t* w = nullptr; const uint16_t* l = nullptr; u64 n = 0; int32_t max_len = 0, strand = 0, so = 0, comp = 0, no_jump = 0, union_mode = 0; bool valid = false; } fld_pending;
   // a prefetch that waits for kernel A of the same batch to finish (launched by align_batch behind kernel A: the fragment-length kernels then
   // run beside k_classify / k_tup_absorb, which leave most of the memory system's request rate unused, instead of underneath kernel A, which
   // lives on it)
   struct { const uint32_t* w = nullptr; const uint16_t* l = nullptr; u64 n = 0; int32_t max_len = 0, strand = 0, so = 0, comp = 0; bool valid = false; } fld_deferred;
+  u32 last_fld_chunks = 0; u64 last_fld_candidates = 0, last_fld_list_overflows = 0; int last_fld_prefetched = 0;   // the last kamd_fld_from_batch call (kamd_profile)
   DBuf pt_label, pt_flag, pt_len, pt_rowpos, pt_nnzpos, pt_off, pt_ids, pt_counts, pt_wcounts, pt_hist, pt_ck_alpha, pt_ck_a;
   DevState host_state{};
   DevState* state_pin = nullptr;   // pinned staging of the read-backs (sync_state)

@@ -917,7 +917,8 @@ int align_batch(kamd_ctx* c, WorkStream& ws, const u32* d_words, const uint16_t*
     if (int rc = fld_launch(c, ffd, q.w, q.l, q.n, (q.max_len + 15) / 16 + 1, (int)kamd_packed_record_words(q.max_len), c->fld_stream)) return rc;
     HIPC(hipEventRecord(c->fld_ev, c->fld_stream));
     c->fld_pending.w = q.w; c->fld_pending.l = q.l; c->fld_pending.n = q.n; c->fld_pending.max_len = q.max_len;
-    c->fld_pending.strand = q.strand; c->fld_pending.so = q.so; c->fld_pending.valid = true;
+    c->fld_pending.strand = q.strand; c->fld_pending.so = q.so; c->fld_pending.comp = q.comp;
+    c->fld_pending.no_jump = c->ix.no_jump; c->fld_pending.union_mode = c->ix.union_mode; c->fld_pending.valid = true;
   }
   c->last_classify_ms = 0.f;
   for (int k = 0; k < chunks; k++) {
@@ -1212,8 +1213,9 @@ extern "C" int kamd_align_stats_get(kamd_ctx* c, kamd_align_stats* s) {
 }
 
 namespace {
-// ~20 000 qualifying pairs at config #3's rate: one pass, with a margin for sparser data
-constexpr u64 FLD_FIRST_CHUNK = 1048576;
+// first prefix: kamd_tuning.fld_first_chunk (default 1048576 items: ~20 000 qualifying pairs at config #3's rate -- one pass, with a margin
+// for sparser data); kamd_fld_prefetch and kamd_fld_from_batch must agree on it, or the prefetched prefix is never the one asked for
+u64 fld_first_chunk(const kamd_ctx* c) { return (u64)std::min(std::max(c->tune.fld_first_chunk, 64), 1048576); }
 constexpr int FLD_CAP_SMALL = 64;   // list entries per item in global scratch (an LDS list of TUPLE_CAP entries sends too many items to
                                     // the re-run, which costs ~1 ms per launch however few they are)
 // buffers for a prefix of n items + k_fld_first / k_fld / k_fld_rank + the copy of the ranked sample, all on stream s (no synchronisation)
@@ -1239,7 +1241,8 @@ int fld_launch(kamd_ctx* c, const FilterDev& fd, const u32* w, const uint16_t* l
   hipLaunchKernelGGL(k_fld_first, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, c->ix, w, l, n, seq_words, rec_words, c->fld_tl.as<int32_t>(),
                      c->fld_card.as<u32>(), cand, head);
   hipLaunchKernelGGL(k_fld, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, c->ix, w, l, (const u64*)cand, n, seq_words, rec_words,
-                     c->fld_scratch.as<u32>(), FLD_CAP_SMALL, fd, c->fld_tl.as<int32_t>(), c->fld_card.as<u32>(), (const u32*)head);
+                     c->fld_scratch.as<u32>(), std::min(std::max(c->tune.fld_list_cap, 1), FLD_CAP_SMALL), fd, c->fld_tl.as<int32_t>(), c->fld_card.as<u32>(),
+                     (const u32*)head);
   const u32 n_blk = (u32)grid_for(n, FLD_RANK_BLOCK * FLD_RANK_PER);
   u32* blk = (u32*)(sample + FLD_WANT);
   hipLaunchKernelGGL(k_fld_count, dim3(n_blk), dim3(FLD_RANK_BLOCK), 0, s, c->fld_tl.as<int32_t>(), c->fld_card.as<u32>(), n, blk);
@@ -1268,7 +1271,7 @@ extern "C" int kamd_fld_prefetch(kamd_ctx* c, const kamd_quant_opts* o, const ui
     HIPC(hipEventCreateWithFlags(&c->fld_ev_in, hipEventDisableTiming));
   }
   if (c->fld_pending.valid) { HIPC(hipStreamSynchronize(c->fld_stream)); c->fld_pending.valid = false; }
-  const u64 n = std::min<u64>(FLD_FIRST_CHUNK, n_items);
+  const u64 n = std::min<u64>(fld_first_chunk(c), n_items);
   // launched by the kamd_pseudoalign call on the same batch, behind its kernel A (align_batch): the fragment-length kernels then run beside
   // k_classify / the tuple de-duplication instead of underneath kernel A, which lives on the memory system's request rate
   c->fld_deferred.w = d_words; c->fld_deferred.l = d_len; c->fld_deferred.n = n; c->fld_deferred.max_len = max_len;
@@ -1293,7 +1296,8 @@ extern "C" int kamd_fld_from_batch(kamd_ctx* c, const kamd_quant_opts* o, const 
   // qualify (config #3: 3.6 % -- one transcript after the filters AND both mates on one block), then size the next prefix
   // from the rate seen so far.  (Matching the prefix with kernel A's FILTER variant + a kernel over its raw records was
   // tried: 0.5 + 1.0 ms per 262 k pairs plus 1.1 ms for the few items whose class list overflows -- not better than k_fld.)
-  u64 chunk = FLD_FIRST_CHUNK;
+  u64 chunk = fld_first_chunk(c);
+  c->last_fld_chunks = 0; c->last_fld_candidates = 0; c->last_fld_list_overflows = 0; c->last_fld_prefetched = 0;
   DBuf &tl = c->fld_tl, &card = c->fld_card, &scratch = c->fld_scratch, &items = c->fld_items;
   std::vector<u64> h_items;
   int rc = 0;
@@ -1302,7 +1306,10 @@ extern "C" int kamd_fld_from_batch(kamd_ctx* c, const kamd_quant_opts* o, const 
     const u32* w = d_words + done * (u64)rec_words * 2;
     const uint16_t* l = d_len + 2 * done;
     const bool prefetched = done == 0 && c->fld_pending.valid && c->fld_pending.w == w && c->fld_pending.l == l && c->fld_pending.n == n &&
-                            c->fld_pending.max_len == max_len && c->fld_pending.strand == o->strand && c->fld_pending.so == o->single_overhang;
+                            c->fld_pending.max_len == max_len && c->fld_pending.strand == o->strand && c->fld_pending.so == o->single_overhang &&
+                            // (the launch read --no-jump / --union / the comprehensive strand filter from the device index as the kamd_pseudoalign
+                            // call in between had set them: a sample taken under other options is not this call's)
+                            c->fld_pending.comp == c->ix.comprehensive && c->fld_pending.no_jump == c->ix.no_jump && c->fld_pending.union_mode == c->ix.union_mode;
     if (c->fld_pending.valid) {   // either consumed now or stale
       if (hipEventSynchronize(c->fld_ev) != hipSuccess) { rc = kamd::fail(-100, "k_fld (prefetched) failed"); break; }
       c->fld_pending.valid = false;
@@ -1314,6 +1321,8 @@ extern "C" int kamd_fld_from_batch(kamd_ctx* c, const kamd_quant_opts* o, const 
     // items with more than FLD_CAP_SMALL distinct transcript sets (the head counts them): same kernel again with the large list,
     // then the sample is taken on the host from the two full vectors
     const u32* head = fld_host_head(c);
+    c->last_fld_chunks++; c->last_fld_candidates += head[0]; c->last_fld_list_overflows += head[1];
+    if (prefetched) c->last_fld_prefetched = 1;
     if (head[1]) {
       int32_t* h_tl = (int32_t*)c->fld_host; u32* h_card = (u32*)c->fld_host + n;
       if (hipMemcpyAsync(h_card, card.p, n * 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { rc = kamd::fail(-100, "k_fld copy failed"); break; }

@@ -640,7 +640,9 @@ int kamd_bus_correct(kamd_ctx*, const kamd_bus_whitelist*, const kamd_bus_record
  * distinct, no two classes with the same transcripts (kamd_ec_upload checks a host CSR for exactly that; a device CSR is not checked).
  * d_weight_counts: the counts the weights w = count/eff_len are
  * computed from (tc_.counts; NULL = d_counts -- they only differ in bootstraps).  eff_lens: host [n_targets].
- * Outputs (host): alpha, alpha_before_zeroes (nullable) [n_targets], rounds ("ran for i rounds"). */
+ * Outputs (host): alpha, alpha_before_zeroes (nullable) [n_targets], rounds ("ran for i rounds").
+ * With s the first round at which nothing changed and s > min_rounds: s + 1 < n_iter: the clamped final round runs, rounds = s + 1; s + 1 == n_iter:
+ * alpha is round s's with the clamp (< 1e-8 -> 0), alpha_before_zeroes is set, rounds = n_iter; no such s: the last round's alpha, alpha_before_zeroes = 0. */
 int kamd_em_run(kamd_ctx*, const uint64_t* d_ec_off, const uint32_t* d_ec_ids, const uint32_t* d_counts,
                 const uint32_t* d_weight_counts, uint64_t n_ecs, const double* eff_lens, uint64_t n_targets, uint32_t n_iter,
                 uint32_t min_rounds, double* alpha, double* alpha_before_zeroes, int32_t* rounds);

@@ -1700,12 +1700,12 @@ __global__ void k_gi_zero_tail(double* p0, double* p1, double* p2, double* p3, d
 }
 // the oversized components' transcripts back in transcript space (behind k_em_scatter, which left them at 0)
 __global__ void k_gi_scatter(u64 T, const u32* __restrict__ mflag, const u64* __restrict__ mpos, const double* __restrict__ fin, const double* __restrict__ before,
-                             int have_final, double* out_alpha, double* out_abz) {
+                             int have_before, int clamp, double* out_alpha, double* out_abz) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T || !mflag[t]) return;
   const u64 m = mpos[t];
-  out_alpha[t] = fin[m];
-  out_abz[t] = have_final ? before[m] : 0.0;
+  out_alpha[t] = clamp ? kamd_em_local::em_clamp_out(fin[m]) : fin[m];
+  out_abz[t] = have_before ? before[m] : 0.0;
 }
 // ---- the oversized component in 2-D blocks: gathers out of LDS -------------------------------------------------------------------------
 // k_gi_rows / k_gi_cols gather one FP64 value per entry through the vector memory pipeline: a 64-byte line travels from L2 for 8 useful
@@ -2422,15 +2422,18 @@ int EmSellGpu::setup(int hist_ints, const double* d_eff_new, u64 T_out) {
   }
   return 0;
 }
-// back to transcript space on the device: a transcript outside m-space keeps its singleton count from round 1 on (0 if in no set)
+// back to transcript space on the device: a transcript outside m-space keeps its singleton count from round 1 on (0 if in no set).
+// have_before: the stop rule held, `before` is alpha_before_zeroes_; clamp: no final round followed it (em_final_round_runs), the result
+// takes the clamp on its way out
 __global__ void k_em_scatter(const u32* __restrict__ mslot, const double* __restrict__ single_all, const double* __restrict__ fin,
-                             const double* __restrict__ before, u64 T, int have_final, double* out_alpha, double* out_abz) {
+                             const double* __restrict__ before, u64 T, int have_before, int clamp, double* out_alpha, double* out_abz) {
   const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= T) return;
   const u32 ms = mslot[t];
   const double sa = single_all[t];
-  out_alpha[t] = ms != 0xFFFFFFFFu ? fin[ms] : sa;
-  out_abz[t] = have_final ? (ms != 0xFFFFFFFFu ? before[ms] : sa) : 0.0;
+  const double v = ms != 0xFFFFFFFFu ? fin[ms] : sa;
+  out_alpha[t] = clamp ? kamd_em_local::em_clamp_out(v) : v;
+  out_abz[t] = have_before ? (ms != 0xFFFFFFFFu ? before[ms] : sa) : 0.0;
 }
 // hands the change counts of the LAST chunk a run can have to the host (no chunk follows it that would)
 __global__ void k_em_publish(EmsPrev prev) {
@@ -2441,22 +2444,11 @@ __global__ void k_em_publish(EmsPrev prev) {
 // ping-pong between two copies of (alpha, a) -- the input of a chunk IS the checkpoint it is replayed from --, chunk k + 1 is queued
 // while chunk k runs, evaluates the stop rule on chunk k's change counts itself (and returns at once if the run stops in k) and
 // publishes them to pinned host memory, which the host polls.  Then: replay up to the stop round, the final round with the clamp
-// (:212-221), the scatter to transcript space, ONE copy to the host.
+// (:212-221) if the loop still has a round for it (em_final_round_runs), the scatter to transcript space, ONE copy to the host.
+// (n_iter >= 1: em_run_impl answers a loop without rounds itself)
 int em_sell_drive_async(kamd_ctx* c, EmSellGpu& B, const SellCache& K, u64 T, int n_iter, int min_rounds, double* alpha_out, double* abz_out, int* rounds_out) {
   const int CH = EML_MAX_ROUNDS;
-  if (n_iter <= 0) {   // no round at all: the initial vector (alpha_ = 1/T), no final round
-    hipLaunchKernelGGL(k_em_scatter, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, K.mslot, K.single_all, B.d_alpha, B.d_alpha, T, 0, B.d_out, B.d_out + T);
-    if (B.gi) hipLaunchKernelGGL(k_gi_scatter, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, B.gi->plan.mflag, B.gi->plan.mpos, B.gi->G_al[0], B.gi->G_al[0], 0,
-                                 B.d_out, B.d_out + T);
-    HIPC(hipGetLastError());
-    std::vector<double> tmp(2 * T);
-    HIPC(hipMemcpyAsync(tmp.data(), B.d_out, 2 * T * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPC(hipStreamSynchronize(c->stream));
-    memcpy(alpha_out, tmp.data(), T * 8);
-    if (abz_out) memcpy(abz_out, tmp.data() + T, T * 8);
-    *rounds_out = 0;
-    return 0;
-  }
+  if (n_iter <= 0) return kamd::fail(-104, "kamd_em_run: the component-local EM was asked for no round");
   const int n_chunks = std::max(1, (n_iter + CH - 1) / CH);
   // pinned, mapped host memory: change counts per chunk | sequence word | result staging
   const size_t hist_ints = (size_t)(n_chunks + 1) * CH;
@@ -2529,7 +2521,8 @@ int em_sell_drive_async(kamd_ctx* c, EmSellGpu& B, const SellCache& K, u64 T, in
   }
   const double* fin; const double* before;
   int rounds;
-  const bool have_final = stop >= 0;
+  const bool have_before = stop >= 0;
+  const bool have_final = have_before && kamd_em_local::em_final_round_runs(stop, n_iter);
   if (have_final) {
     const int s = decided, base = s * CH;
     // (chunk s + 1, queued behind s, saw the stop and left its output -- the input of s -- alone)
@@ -2538,12 +2531,15 @@ int em_sell_drive_async(kamd_ctx* c, EmSellGpu& B, const SellCache& K, u64 T, in
     before = al[(s + 1) & 1]; fin = al[s & 1];   // what the final round read is alpha_before_zeroes_
     rounds = stop + 1;
   } else {
+    // the loop ran out, or the stop rule held in its last round (stop == n_iter - 1: the last chunk ended on it, nothing to replay and no
+    // round left for the final one): the result is what the last chunk wrote, with the clamp on the way out in the second case
     fin = al[n_chunks & 1]; before = fin;
     rounds = n_iter;
   }
-  hipLaunchKernelGGL(k_em_scatter, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, K.mslot, K.single_all, fin, before, T, have_final ? 1 : 0, B.d_out, B.d_out + T);
+  const int clamp_out = have_before && !have_final ? 1 : 0;
+  hipLaunchKernelGGL(k_em_scatter, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, K.mslot, K.single_all, fin, before, T, have_before ? 1 : 0, clamp_out, B.d_out, B.d_out + T);
   if (B.gi) hipLaunchKernelGGL(k_gi_scatter, dim3(grid_for(T, BLOCK)), dim3(BLOCK), 0, c->stream, T, B.gi->plan.mflag, B.gi->plan.mpos, B.gi->G_al[B.gi_par(fin)],
-                               B.gi->G_al[B.gi_par(before)], have_final ? 1 : 0, B.d_out, B.d_out + T);
+                               B.gi->G_al[B.gi_par(before)], have_before ? 1 : 0, clamp_out, B.d_out, B.d_out + T);
   HIPC(hipGetLastError());
   HIPC(hipMemcpyAsync(h_out, B.d_out, 2 * T * 8, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
@@ -3005,7 +3001,8 @@ int em_sell_run_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, co
   if (int rc = B.setup(multi ? chunk : n_chunks * chunk, K.dev.eff, multi ? 0 : T)) return rc;
   int r = 0;
   if (multi) {
-    r = kamd_em_local::run(B, P, n_iter, min_rounds, chunk, alpha, abz);   // the change counts of a chunk are summed over the ranks before anyone reads them
+    int stop = -1;
+    r = kamd_em_local::run(B, P, n_iter, min_rounds, chunk, alpha, abz, &stop);   // the change counts of a chunk are summed over the ranks before anyone reads them
     if (K.hybrid && !B.err) {
       // the oversized components' transcripts (kamd_em_local::run scattered the groups' and left these at their singleton counts)
       const PmPlan& GP = K.G.plan;
@@ -3013,10 +3010,13 @@ int em_sell_run_device(kamd_ctx* c, const u64* d_ec_off, const u32* d_ec_ids, co
       HIPC(hipMemcpyAsync(mflag.data(), GP.mflag, T * 4, hipMemcpyDeviceToHost, c->stream));
       HIPC(hipMemcpyAsync(mpos.data(), GP.mpos, T * 8, hipMemcpyDeviceToHost, c->stream));
       HIPC(hipStreamSynchronize(c->stream));
-      const bool have_final = B.host_reads >= 2;   // (the state before the final round was read, then the final one)
+      // (host_alpha() was read before the final round and after it; if the stop rule held in the loop's last round, once: that state is
+      // alpha_before_zeroes_ and, clamped, the result)
+      const bool have_before = stop >= 0, have_final = have_before && kamd_em_local::em_final_round_runs(stop, n_iter);
       for (u64 t = 0; t < T; t++) if (mflag[t]) {
-        alpha[t] = B.h_gi_cur[mpos[t]];
-        if (abz) abz[t] = have_final ? B.h_gi_prev[mpos[t]] : 0.0;
+        const double v = B.h_gi_cur[mpos[t]];
+        alpha[t] = have_before && !have_final ? kamd_em_local::em_clamp_out(v) : v;
+        if (abz) abz[t] = have_final ? B.h_gi_prev[mpos[t]] : have_before ? v : 0.0;
       }
     }
   }
@@ -3114,6 +3114,14 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
   const u32* d_wcounts = d_weight_counts ? d_weight_counts : d_counts;
   const u64 T = n_targets;
   if (T == 0) return kamd::fail(-1, "kamd_em_run: no targets");
+  if (n_iter == 0) {   // a loop without rounds, in every form: alpha_ = 1/T (:38), alpha_before_zeroes_ untouched, i = 0
+    const double a0 = part.rank == 0 ? 1.0 / (double)T : 0.0;   // (several ranks: the caller sums the ranks' vectors)
+    for (u64 t = 0; t < T; t++) alpha[t] = a0;
+    if (alpha_before_zeroes) memset(alpha_before_zeroes, 0, T * sizeof(double));
+    if (rounds) *rounds = 0;
+    c->last_em_ms = 0.f; c->last_em_iters = 0;
+    return 0;
+  }
   const bool spec = part.world > 1;
   if (spec && n_ecs) {
     EmCsr local{};
@@ -3243,6 +3251,7 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
     return 0;
   };
   EmNow now{};
+  bool clamp_out = false;   // the stop rule held in the loop's last round: no final round ran (em_final_round_runs), the result takes the clamp on its way out
   if (!spec) {
     bool use_graph = c->tune.em_graph != 2;
     hipGraph_t graph = nullptr; hipGraphExec_t gexec = nullptr;
@@ -3265,7 +3274,11 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
     }
     if (gexec) (void)hipGraphExecDestroy(gexec);
     if (graph) (void)hipGraphDestroy(graph);
-    hs.done = 1; hs.rounds = now.rounds; hs.final_round = now.fin;
+    // now.fin says that the stop rule held: the final round then ran as round stop + 1 = now.rounds, unless the loop ended first
+    // (now.rounds == n_iter; the kernels of a round that is past the loop's end return at once)
+    hs.done = 1; hs.rounds = now.rounds;
+    hs.final_round = now.fin && kamd_em_local::em_final_round_runs(now.rounds - 1, (int)n_iter) ? 1 : 0;
+    clamp_out = now.fin && !hs.final_round;
   } else {
     // Partitioned EM: run a chunk of rounds speculatively, sum the per-round change counts over the ranks (the callback;
     // also the only synchronisation between ranks), find the first round s at which the reference's test
@@ -3289,6 +3302,10 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
         base += n_run;
         if (base >= (int)n_iter) { hs.done = 1; hs.rounds = (int)n_iter; hs.final_round = 0; break; }  // the loop ran out
         continue;
+      }
+      if (!kamd_em_local::em_final_round_runs(stop, (int)n_iter)) {   // stop is the loop's last round: the chunk ended on it, nothing to replay
+        hs.done = 1; hs.rounds = (int)n_iter; hs.final_round = 0; clamp_out = true;
+        break;
       }
       // rewind + replay rounds base..stop, then the clamped final round
       if (int rc = checkpoint(base & 1, true)) return rc;
@@ -3318,15 +3335,18 @@ int em_run_impl(kamd_ctx* c, const uint64_t* d_ec_off, const uint32_t* d_ec_ids,
   HIPC(hipEventSynchronize(c->ev1));
   HIPC(hipEventElapsedTime(&c->last_em_ms, c->ev0, c->ev1));
   c->last_em_iters = (uint64_t)hs.rounds + (hs.final_round ? 1 : 0);
-  // result = the buffer the last executed round wrote; alpha_before_zeroes = the (unclamped) buffer it read
+  // result = the buffer the last executed round wrote; alpha_before_zeroes = the (unclamped) buffer it read if that was the final round,
+  // the result itself before the clamp if the stop rule held in the loop's last round, unset if it never held
   double* bufs[2] = {c->em_alpha.as<double>(), c->em_next.as<double>()};
   const int last_read = hs.final_round ? (hs.rounds & 1) : ((hs.rounds - 1) & 1);
   HIPC(hipMemcpyAsync(alpha, bufs[last_read ^ 1], T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (alpha_before_zeroes) {
-    if (hs.final_round) HIPC(hipMemcpyAsync(alpha_before_zeroes, bufs[last_read], T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (hs.final_round || clamp_out)
+      HIPC(hipMemcpyAsync(alpha_before_zeroes, bufs[clamp_out ? last_read ^ 1 : last_read], T * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     else memset(alpha_before_zeroes, 0, T * sizeof(double));
   }
   HIPC(hipStreamSynchronize(c->stream));
+  if (clamp_out) for (u64 t = 0; t < T; t++) alpha[t] = kamd_em_local::em_clamp_out(alpha[t]);
   if (rounds) *rounds = hs.rounds;
   return 0;
 }

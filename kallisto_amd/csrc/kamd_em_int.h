@@ -27,7 +27,9 @@ __host__ __device__ inline EmNow em_next_round(const EmState& prev, int n_iter, 
   const bool stopEM = !spec && prev.chcount == 0 && prev.iter > min_rounds;          // :202-205
   n.it = prev.iter + 1;
   n.fin = (stopEM || prev.force_final) ? 1 : 0;                                      // :212-221 (clamp applied on read)
-  if (n.it >= n_iter) { n.done = 1; n.rounds = n_iter; }                             // the loop ran out
+  // the loop ran out: round n.it does not run.  With n.fin set it would have been the final round -- the host tells the two apart by
+  // rounds == n_iter (kamd_em_local::em_final_round_runs) and clamps the result of round n_iter - 1 itself
+  if (n.it >= n_iter) { n.done = 1; n.rounds = n_iter; }
   return n;
 }
 struct Carver {  // sub-allocations of one device arena, 256-byte aligned

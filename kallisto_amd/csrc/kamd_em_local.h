@@ -8,7 +8,8 @@
 // two kernel boundaries and two dependent global round trips per round: 25.5 us).
 // Only the stop rule "chcount == 0 && i > min_rounds" (:202-205) is global.  It is handled like kamd_em_run_partitioned
 // does across ranks: a chunk of rounds runs speculatively from a checkpoint while every group adds its per-round change
-// count to a history, the first qualifying round is found, the chunk is replayed up to it, then the clamped final round.
+// count to a history, the first qualifying round is found, the chunk is replayed up to it, then the clamped final round -- if the
+// loop still has a round for it (em_final_round_runs below).
 //
 // This header holds what can be checked without a GPU (tests/emu, tests/test_em_local.py):
 //   * the plan (groups, local CSR in both directions) and a host reference builder for it,
@@ -562,13 +563,26 @@ struct CpuBackend {
 };
 
 // ---- the driver: EMAlgorithm::run's loop control over a backend that can only run whole chunks ----------------------
-// alpha_out / abz_out: [T].  Returns the number of rounds ("ran for i rounds").
+// The loop's end, stated ONCE for every host driver (this one, em_sell_drive_async, the read-out and the partitioned replay of
+// em_run_impl).  `stop` is the first round with chcount == 0 && stop > min_rounds (:202-205).  The clamped final round (:212-221) is
+// round stop + 1, so it runs iff the loop still has that round.  If it has not (stop is then the loop's last round, n_iter - 1), the
+// loop ends with what round `stop` left: alpha_before_zeroes_ is set, alpha_ has the clamp applied, and i == n_iter.
+KAMD_HD bool em_final_round_runs(int stop, int n_iter) { return stop + 1 < n_iter; }
+KAMD_HD double em_clamp_out(double alpha) { return alpha < 1e-7 / 10.0 ? 0.0 : alpha; }   // :217-219, applied to a result on its way out
+
+// alpha_out / abz_out: [T].  Returns the number of rounds ("ran for i rounds").  stop_out (if given): the round the stop rule first held
+// in, -1 if the loop ran out before it did.
 template <class Backend, class PlanT>
-int run(Backend& B, const PlanT& P, int n_iter, int min_rounds, int chunk, double* alpha_out, double* abz_out) {
+int run(Backend& B, const PlanT& P, int n_iter, int min_rounds, int chunk, double* alpha_out, double* abz_out, int* stop_out = nullptr) {
   const uint64_t M = P.tr_base[P.n_groups];
+  if (stop_out) *stop_out = -1;
+  if (n_iter <= 0) {   // no round at all: alpha_ = 1/T for every transcript (:38), nothing else set
+    for (uint64_t t = 0; t < P.T; t++) { alpha_out[t] = 1.0 / (double)P.T; if (abz_out) abz_out[t] = 0.0; }
+    return 0;
+  }
   std::vector<int> hist((size_t)chunk);
   int base = 0, rounds = 0;
-  bool have_final = false;
+  bool have_before = false, clamp_out = false;
   std::vector<double> before;
   for (;;) {
     const int n = std::min(chunk, n_iter - base);
@@ -582,20 +596,28 @@ int run(Backend& B, const PlanT& P, int n_iter, int min_rounds, int chunk, doubl
       if (base >= n_iter) { rounds = n_iter; break; }            // the loop ran out: no final round
       continue;
     }
+    if (stop_out) *stop_out = stop;
+    have_before = true;
+    if (!em_final_round_runs(stop, n_iter)) {                    // stop is the loop's last round: the chunk ended on it, nothing to replay
+      const std::vector<double>& cur = B.host_alpha();
+      before.assign(cur.begin(), cur.begin() + M);
+      clamp_out = true;
+      rounds = n_iter;
+      break;
+    }
     B.restore();
     B.run(stop - base + 1, 0, nullptr);                          // replay rounds base..stop
     { const std::vector<double>& cur = B.host_alpha(); before.assign(cur.begin(), cur.begin() + M); }   // what the final round reads: alpha_before_zeroes_
     B.run(1, 1, nullptr);                                        // the final round (:212-221, clamp applied on read)
-    have_final = true;
     rounds = stop + 1;
     break;
   }
   // back to transcript space: a transcript outside m-space keeps its singleton count from round 1 on (0 if in no set)
-  for (uint64_t t = 0; t < P.T; t++) { alpha_out[t] = P.single_all[t]; if (abz_out) abz_out[t] = have_final ? P.single_all[t] : 0.0; }
-  const std::vector<double>& fin = B.host_alpha();
+  for (uint64_t t = 0; t < P.T; t++) { alpha_out[t] = P.single_all[t]; if (abz_out) abz_out[t] = have_before ? P.single_all[t] : 0.0; }
+  const std::vector<double>& fin = clamp_out ? before : B.host_alpha();
   for (uint64_t m = 0; m < M; m++) {
-    alpha_out[P.tr_id[m]] = fin[m];
-    if (abz_out) abz_out[P.tr_id[m]] = have_final ? before[m] : 0.0;
+    alpha_out[P.tr_id[m]] = clamp_out ? em_clamp_out(fin[m]) : fin[m];
+    if (abz_out) abz_out[P.tr_id[m]] = have_before ? before[m] : 0.0;
   }
   return rounds;
 }

@@ -24,6 +24,7 @@
  *       (the technology table and ParseTechnology, src/main.cpp:1283-1408, 778-870 -> kamd_bus_layout_parse)
  *       `bustools sort | bustools count` between those records and quant-tcc (not part of the reference) -> kamd_bus_sort, kamd_bus_count
  *       `bustools correct` in front of them (not part of the reference either) -> kamd_bus_whitelist_create, kamd_bus_correct
+ *       `bustools count --genecounts` behind them (not part of the reference either) -> kamd_bus_genes_create, kamd_bus_count_genes
  *   S3  EMAlgorithm ctor + run                   src/EMAlgorithm.h:26-48,95-223   -> kamd_em_run
  *   S4  Bootstrap::run_em / Multinomial::sample  src/Bootstrap.cpp:4-14, src/Multinomial.hpp:33-51 -> kamd_bootstrap, kamd_bootstrap_batch
  *       (the replicate pool of src/Bootstrap.cpp:15-92, src/main.cpp:2764-2782)
@@ -124,7 +125,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 12
+#define KAMD_ABI_VERSION 13
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -633,6 +634,43 @@ int kamd_bus_whitelist_create(kamd_ctx*, const uint64_t* h_codes, uint64_t n, in
 int kamd_bus_whitelist_free(kamd_ctx*, kamd_bus_whitelist*);
 int kamd_bus_correct(kamd_ctx*, const kamd_bus_whitelist*, const kamd_bus_record* d_in, uint64_t n, kamd_bus_record* d_out /* [n] */,
                      uint8_t* d_status /* nullable, [n] */, uint64_t* n_out /* host */, kamd_bus_correct_stats* stats /* nullable */);
+
+/* ---- BUS records -> a cells x genes matrix: what `bustools count --genecounts -g t2g.txt` does, on the device ----
+ * The step behind kamd_bus_sort for a user who wants genes, beside kamd_bus_count.  The rules (kamd_busgenes.h restates them):
+ *   - gene map: every transcript has a gene id in [0, n_genes), or -1 for no gene.
+ *   - gene list G of a class: the sorted, distinct gene ids (>= 0) of its transcripts; a transcript without a gene adds nothing; G may be empty.
+ *   - KAMD_BUS_COUNT_UMIS: rows and groups are kamd_bus_count's.  I = the intersection of G over a group's records, single-class groups included.
+ *     |I| = 1: the group adds 1 to (row, that gene); |I| = 0: dropped (no gene); |I| >= 2: dropped (multi-gene).
+ *   - KAMD_BUS_COUNT_READS: every record is its own group; a record whose class has |G| = 1 adds its count to (row, gene).
+ * How bustools treats a transcript that the t2g file does not name has not been checked; the rule is this project's, held to a restatement.
+ *
+ * kamd_bus_genes_create: the map h_tr_gene[0 .. n_targets) and the classes as a CSR (h_ec_off[n_classes + 1], h_ec_ids; all host) are checked
+ * (-1: a gene that is neither -1 nor below n_genes, a transcript id >= n_targets, offsets that decrease or do not begin at 0), uploaded, and the
+ * lists are built on the device on the context stream: one key {class, gene} per entry with a gene, kamd_bus_sort's passes and collapse over the
+ * keys, the offsets by class.  Three synchronisations; a plan step, once per run.  Scratch while it runs: 32 bytes per entry.  stats (nullable):
+ * n_pairs = distinct (class, gene), n_empty = classes without a gene, max_list = the longest list.  A context holds any number of tables;
+ * kamd_ctx_destroy frees those not freed by kamd_bus_genes_free.  kamd_bus_genes_download: the table's CSR to the host (h_off[n_classes + 1],
+ * h_ids[n_pairs]); for tests and diagnostics.
+ *
+ * kamd_bus_count_genes: d_sorted[0 .. n) in key order -> d_barcodes[0 .. n_barcodes): the rows; d_entries[0 .. n_entries): the matrix, .ec holds
+ * the gene id, sorted by (row, gene) and unique.  Both are device buffers of n elements.  Errors, each -4 with a text and nothing written: a record
+ * whose class is outside [0, n_classes) of the table, an adjacent pair out of key order, a value above 0xFFFFFFFF.  A table of another context: -1.
+ * One thread per group settles groups of one record and small groups (at most GENES_THREAD_MAX_RECORDS records, smallest list at most
+ * GENES_THREAD_MAX_LIST genes: kamd_busgenes.h); every other group gets a wavefront (n_wave_groups).  Counted groups become unit records that go
+ * through kamd_bus_sort's passes and collapse, as in kamd_bus_count; three synchronisations of the context stream in all.  n_umis: all groups (READS:
+ * all records) = n_counted + n_no_gene + n_multi_gene.  last_ms = the call, resolve_ms = the two resolve kernels' part of it, by HIP events.  The
+ * output is the same bytes on every run.  Scratch, kept in the context: 16 bytes per record beside kamd_bus_count's unit records and group starts.
+ * Same guarantees as kamd_bus_sort: touches neither the EC state, the counts, the tuple table nor the fragment-length sample. */
+typedef struct kamd_bus_genes kamd_bus_genes;
+typedef struct { uint64_t n_classes, n_entries_in, n_pairs /* distinct (class, gene) */, n_empty /* classes with no gene */; uint32_t max_list; int32_t n_genes; float last_ms; } kamd_bus_genes_stats;
+typedef struct { uint64_t n_records, n_barcodes, n_entries, n_umis, n_counted, n_no_gene, n_multi_gene, n_wave_groups; float last_ms, resolve_ms; } kamd_bus_gene_count_stats;
+int kamd_bus_genes_create(kamd_ctx*, const int32_t* h_tr_gene /* [n_targets], -1 = none */, uint64_t n_targets, int32_t n_genes,
+                          const uint64_t* h_ec_off /* [n_classes + 1] */, const uint32_t* h_ec_ids, uint64_t n_classes,
+                          kamd_bus_genes** out, kamd_bus_genes_stats* stats /* nullable */);
+int kamd_bus_genes_free(kamd_ctx*, kamd_bus_genes*);
+int kamd_bus_genes_download(kamd_ctx*, const kamd_bus_genes*, uint64_t* h_off /* [n_classes + 1] */, int32_t* h_ids /* [n_pairs] */);
+int kamd_bus_count_genes(kamd_ctx*, const kamd_bus_genes*, const kamd_bus_record* d_sorted, uint64_t n, int mode,
+                         uint64_t* d_barcodes /* [n] */, kamd_bus_entry* d_entries /* [n]; .ec holds the gene id */, kamd_bus_gene_count_stats* out /* nullable */);
 
 /* ---- S3: EM ---- */
 /* Runs EMAlgorithm(counts, ...).run(n_iter, min_rounds) (src/EMAlgorithm.h:26-48,95-223) on the finalized EC result

@@ -63,7 +63,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 12   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 13   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -171,6 +171,18 @@ class _BusCorrectStats(C.Structure):
                 ("n_out", C.c_uint64), ("last_ms", C.c_float), ("neigh_ms", C.c_float)]
 
 
+class _BusGenesStats(C.Structure):
+    """kamd_bus_genes_stats"""
+    _fields_ = [("n_classes", C.c_uint64), ("n_entries_in", C.c_uint64), ("n_pairs", C.c_uint64), ("n_empty", C.c_uint64), ("max_list", C.c_uint32), ("n_genes", C.c_int32),
+                ("last_ms", C.c_float)]
+
+
+class _BusGeneCountStats(C.Structure):
+    """kamd_bus_gene_count_stats"""
+    _fields_ = [("n_records", C.c_uint64), ("n_barcodes", C.c_uint64), ("n_entries", C.c_uint64), ("n_umis", C.c_uint64), ("n_counted", C.c_uint64),
+                ("n_no_gene", C.c_uint64), ("n_multi_gene", C.c_uint64), ("n_wave_groups", C.c_uint64), ("last_ms", C.c_float), ("resolve_ms", C.c_float)]
+
+
 BUS_COR_EXACT, BUS_COR_CORRECTED, BUS_COR_AMBIGUOUS, BUS_COR_UNCORRECTABLE = 0, 1, 2, 3   # KAMD_BUS_COR_*
 
 
@@ -184,6 +196,27 @@ class BusWhitelist:
     def free(self):
         if self._h is not None and self._ctx._h is not None:
             _check(load_library().kamd_bus_whitelist_free(self._ctx._h, self._h), "kamd_bus_whitelist_free")
+        self._h = None
+
+
+class BusGenes:
+    """a gene table of a Context (kamd_bus_genes): the handle Context.bus_count_genes takes and what kamd_bus_genes_create reported (n_classes,
+    n_entries_in, n_pairs, n_empty, max_list, n_genes, ms).  Context.close frees it; free() does so earlier."""
+
+    def __init__(self, ctx, handle, stats):
+        self._ctx, self._h, self.stats, self.n_genes, self.n_classes = ctx, handle, stats, stats["n_genes"], stats["n_classes"]
+
+    def lists(self):
+        """kamd_bus_genes_download: the table's CSR -> (off uint64 [n_classes + 1], ids int32 [n_pairs]) on the host"""
+        if self._h is None or self._ctx._h is None:
+            raise KallistoAmdError("BusGenes.lists: the table was freed")
+        off, ids = np.zeros(self.n_classes + 1, np.uint64), np.zeros(max(self.stats["n_pairs"], 1), np.int32)
+        _check(load_library().kamd_bus_genes_download(self._ctx._h, self._h, off.ctypes.data, ids.ctypes.data), "kamd_bus_genes_download")
+        return off, ids[:self.stats["n_pairs"]]
+
+    def free(self):
+        if self._h is not None and self._ctx._h is not None:
+            _check(load_library().kamd_bus_genes_free(self._ctx._h, self._h), "kamd_bus_genes_free")
         self._h = None
 
 
@@ -302,6 +335,10 @@ _SYMBOLS = {
     "kamd_bus_whitelist_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(_BusWhitelistStats)]),
     "kamd_bus_whitelist_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kamd_bus_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(_BusCorrectStats)]),
+    "kamd_bus_genes_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(_BusGenesStats)]),
+    "kamd_bus_genes_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "kamd_bus_genes_download": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kamd_bus_count_genes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(_BusGeneCountStats)]),
     "kamd_em_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                               C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "kamd_em_run_partitioned": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32,
@@ -415,6 +452,39 @@ def bus_whitelist_read(path: str):
         return bus_whitelist_parse(data)
     except KallistoAmdError as e:
         raise KallistoAmdError(f"{path}: {e}") from None
+
+
+def genemap_read(path: str, target_names):
+    """a transcripts-to-genes file (`-g`) -> (tr_gene int32 [n_targets], -1 = no gene; gene names; common names), by the rules and with the messages
+    of the C++ front-end's parser (kamd_genes.h parse_genemap): columns separated by white space, genes numbered by first appearance, the last
+    line of a transcript named twice wins, the first of equal target names wins.  Raises KallistoAmdError."""
+    tr_of = {}
+    for i, name in enumerate(target_names):
+        tr_of.setdefault(name, i)
+    tr_gene = np.full(len(target_names), -1, np.int32)
+    gene_of, names, common = {}, [], []
+    try:
+        f = open(path, "r")
+    except OSError:
+        raise KallistoAmdError(f"Error: could not open file {path}") from None
+    with f:
+        for line in f:
+            line = line.rstrip("\n")
+            if not line:
+                continue
+            cols = (line.split() + ["", "", ""])[:3]
+            if not cols[1]:
+                raise KallistoAmdError(f"Error: No gene associated with transcript {cols[0]} in {path}")
+            t = tr_of.get(cols[0])
+            if t is None:
+                raise KallistoAmdError(f"Error: Invalid transcript: {cols[0]} in {path}")
+            g = gene_of.get(cols[1])
+            if g is None:
+                g = gene_of[cols[1]] = len(names)
+                names.append(cols[1])
+                common.append(cols[2])
+            tr_gene[t] = g
+    return tr_gene, names, common
 
 
 def packed_record_words(max_len: int) -> int:
@@ -757,6 +827,51 @@ class Context:
         stats = {"n_records": int(st.n_records), "n_barcodes": int(st.n_barcodes), "n_entries": int(st.n_entries), "n_umis": int(st.n_umis),
                  "n_multi_groups": int(st.n_multi_groups), "n_multi_records": int(st.n_multi_records), "ms": float(st.last_ms)}
         return {"barcodes": barcodes[:stats["n_barcodes"]], "entries": entries[:stats["n_entries"]], "multi": multi[:stats["n_multi_records"]], "stats": stats}
+
+    # ---- BUS records -> cells x genes (bustools count --genecounts) ----
+    def bus_genes(self, tr_gene, n_genes: int, ec_sets_or_csr) -> BusGenes:
+        """kamd_bus_genes_create: a gene map (int32 per transcript, -1 = no gene) and the classes the records name -- a sequence of transcript-id
+        sequences, or a CSR (ec_off [n_classes + 1], ec_ids) -- -> a BusGenes whose gene lists lie on the device."""
+        tr_gene = np.ascontiguousarray(tr_gene, np.int32)
+        if isinstance(ec_sets_or_csr, tuple) and len(ec_sets_or_csr) == 2 and isinstance(ec_sets_or_csr[0], np.ndarray):
+            ec_off, ec_ids = ec_sets_or_csr
+        else:
+            sets = list(ec_sets_or_csr)
+            ec_off = np.zeros(len(sets) + 1, np.uint64)
+            if sets:
+                ec_off[1:] = np.cumsum([len(x) for x in sets], dtype=np.uint64)
+            ec_ids = np.fromiter((t for x in sets for t in x), np.int64, int(ec_off[-1]))
+            if len(ec_ids) and (int(ec_ids.min()) < 0 or int(ec_ids.max()) > 0xFFFFFFFF):
+                raise KallistoAmdError("bus_genes: a transcript id outside 32 bits")
+        ec_off, ec_ids = np.ascontiguousarray(ec_off, np.uint64), np.ascontiguousarray(ec_ids, np.uint32)
+        if len(ec_off) < 1:
+            raise KallistoAmdError("bus_genes: the offsets need n_classes + 1 entries")
+        h, st = C.c_void_p(None), _BusGenesStats()
+        _check(load_library().kamd_bus_genes_create(self._h, tr_gene.ctypes.data if len(tr_gene) else None, len(tr_gene), int(n_genes), ec_off.ctypes.data,
+                                                    ec_ids.ctypes.data if len(ec_ids) else None, len(ec_off) - 1, C.byref(h), C.byref(st)), "kamd_bus_genes_create")
+        return BusGenes(self, h, {"n_classes": int(st.n_classes), "n_entries_in": int(st.n_entries_in), "n_pairs": int(st.n_pairs), "n_empty": int(st.n_empty),
+                                  "max_list": int(st.max_list), "n_genes": int(st.n_genes), "ms": float(st.last_ms)})
+
+    def bus_count_genes(self, genes: BusGenes, sorted_records, mode: int) -> dict:
+        """kamd_bus_count_genes: records in key order (Context.bus_sort) whose classes the table knows -> barcodes (int64 [n_barcodes]: the rows),
+        entries (int32 [n_entries, 3]: kamd_bus_entry with the gene id in `ec`, see bus_entries_numpy; sorted by (row, gene), unique) and stats.
+        mode: BUS_COUNT_UMIS or BUS_COUNT_READS.  Unsorted input and a class outside the table raise."""
+        torch = self.torch
+        dev = f"cuda:{self.device}"
+        n = int(sorted_records.shape[0])
+        if n and not sorted_records.is_contiguous():
+            raise KallistoAmdError("bus_count_genes: the records must be a contiguous int64 [n, 4] tensor")
+        if genes._h is None or genes._ctx is not self:
+            raise KallistoAmdError("bus_count_genes: not a (live) gene table of this context")
+        m = max(n, 1)
+        barcodes = torch.empty(m, dtype=torch.int64, device=dev)
+        entries = torch.empty((m, 3), dtype=torch.int32, device=dev)
+        st = _BusGeneCountStats()
+        _check(load_library().kamd_bus_count_genes(self._h, genes._h, sorted_records.data_ptr() if n else None, n, int(mode), barcodes.data_ptr(), entries.data_ptr(),
+                                                   C.byref(st)), "kamd_bus_count_genes")
+        stats = {k: int(getattr(st, k)) for k, _ in _BusGeneCountStats._fields_ if k not in ("last_ms", "resolve_ms")}
+        stats["ms"], stats["resolve_ms"] = float(st.last_ms), float(st.resolve_ms)
+        return {"barcodes": barcodes[:stats["n_barcodes"]], "entries": entries[:stats["n_entries"]], "stats": stats}
 
     # ---- barcode whitelists (bustools correct) ----
     def bus_whitelist(self, codes_or_path, bc_len: int | None = None) -> BusWhitelist:

@@ -1,6 +1,6 @@
 """`kallisto bus -x <technology>` over the library: a small Python driver that writes a `kallisto bus` output directory for a barcode / UMI technology.
 
-    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] [--count] [-w WHITELIST] files...
+    python -m kallisto_amd.bus_sc -x TECH -i index.idx -o out [--fr-stranded|--rf-stranded|--unstranded] [--no-jump] [--union] [--bus-per-read] [--count] [--genecounts -g T2G] [-w WHITELIST] files...
 
 TECH is a technology name (10XV3, SURECELL, INDROPSV2, VASA-SEQ, ...) or a custom "bc:umi:seq" string (BusLayout.parse); the files come in sets of the
 technology's file count, plain or gzip.  Per batch of UNIT_RECORDS read sets the driver runs
@@ -20,6 +20,16 @@ is counted on the device (kamd_bus_count: distinct UMIs per (barcode, class), or
 several classes is resolved here as bustools does: the transcript sets of its classes are intersected, an empty intersection drops the UMI,
 otherwise it counts 1 for the class of the intersection, which is appended to matrix.ec when it is new.  `kallisto_amd_quant quant-tcc -e
 counts/output.ec.txt counts/output.mtx` takes the result.
+
+--genecounts -g T2G: what `bustools count --genecounts -g T2G` makes of output.bus, into out/genes/: output.mtx (rows = barcodes, columns = genes in
+the order of their first appearance in T2G, the layout of --count's file), output.barcodes.txt, output.genes.txt and count.json.  T2G names a gene
+for transcripts of the index (white-space separated columns: transcript, gene[, common name]); a transcript it does not name has no gene.  After the
+last merge the gene lists of the run's classes are built on the device (kamd_bus_genes_create) and the run's records are counted there
+(kamd_bus_count_genes): per UMI the gene lists of its classes are intersected, exactly one gene left counts 1 for it, none or several drop the UMI;
+where the layout has no UMI every record whose class has one gene adds its count.  No record is looked at on the host.  The counters (n_barcodes,
+n_umis, n_counted, n_no_gene, n_multi_gene) go into genes/count.json and, with the prefix genes_, into the dict run() returns.  Works with or
+without --count (the classes --count appends to matrix.ec are named by no record).  Refused: --genecounts without -g, -g without --genecounts, a bad
+map (the parser's text).
 
 -w / --whitelist FILE: what `bustools correct` does between the records and their sort.  FILE lists the technology's barcodes, one per line, plain
 or gzip.  Every batch's records go through kamd_bus_correct: a record whose barcode is on the list is kept, one whose barcode is one substitution
@@ -89,8 +99,12 @@ def _pack_unit(ctx, texts, n_records, n_files):
 
 
 def run(technology, index_path, out_dir, files, strand=None, no_jump=False, union=False, per_read=False, unit_records=UNIT_RECORDS, device=0, call="", count=False,
-        merge_records=MERGE_RECORDS, whitelist=None):
+        merge_records=MERGE_RECORDS, whitelist=None, genecounts=False, genemap=None):
     layout, default_strand = A.BusLayout.parse(technology)
+    if genecounts and not genemap:
+        raise A.KallistoAmdError("--genecounts needs a transcripts-to-genes file: -g FILE")
+    if genemap and not genecounts:
+        raise A.KallistoAmdError("-g/--genemap is only used with --genecounts")
     wl_codes = _read_whitelist(whitelist, layout, technology) if whitelist else None
     if strand is None:
         strand = default_strand
@@ -98,6 +112,7 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
         raise A.KallistoAmdError(f"Number of files ({len(files)}) does not match number of input files required by technology {technology} ({layout.n_files})")
     start_time = time.ctime()
     index = A.Index(index_path)
+    gm = A.genemap_read(genemap, index.target_names()) if genecounts else None   # (a bad map: refused before anything runs)
     ctx = A.Context(device)
     ctx.upload(index)
     opts = A.QuantOpts(0, 200.0, 20.0, 1, strand, 1 if no_jump else 0, 1 if union else 0)   # what `bus` runs single-end reads with
@@ -168,6 +183,7 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
     rec = A.bus_records_numpy(d_all)
     bclen, umilen = layout.header_lens(bc_hist, umi_hist)
     os.makedirs(out_dir, exist_ok=True)
+    gene_counted = _genecount(ctx, d_all, layout, gm, ec_sets, bclen, os.path.join(out_dir, "genes")) if genecounts else {}   # (before --count: the run's own classes)
     counted = _count(ctx, d_all, layout, ec_of, ec_sets, bclen, os.path.join(out_dir, "counts")) if count else {}
     text = b"BUS file produced by kallisto"
     with open(os.path.join(out_dir, "output.bus"), "wb") as f:
@@ -191,6 +207,7 @@ def run(technology, index_path, out_dir, files, strand=None, no_jump=False, unio
             json.dump(corrected, f, indent=1)
             f.write("\n")
         counted = dict(counted, **corrected)
+    counted = dict(counted, **{"genes_" + k: v for k, v in gene_counted.items()})
     info = dict(info, **counted)   # (run_info.json keeps the reference's keys)
     return info
 
@@ -264,6 +281,38 @@ def _count(ctx, d_rec, layout, ec_of, ec_sets, bclen, out_dir):
     return {"n_barcodes": st["n_barcodes"], "n_umis": st["n_umis"], "n_multi_umis": st["n_multi_groups"]}
 
 
+GENE_KEYS = ("n_barcodes", "n_umis", "n_counted", "n_no_gene", "n_multi_gene")
+
+
+def _genecount(ctx, d_rec, layout, gm, ec_sets, bclen, out_dir):
+    """the run's sorted records -> out_dir/output.mtx, output.barcodes.txt, output.genes.txt, count.json; gm = genemap_read's result"""
+    tr_gene, names, _ = gm
+    table = ctx.bus_genes(tr_gene, len(names), ec_sets)
+    try:
+        c = ctx.bus_count_genes(table, d_rec, count_mode(layout))
+    finally:
+        table.free()
+    ent = A.bus_entries_numpy(c["entries"])
+    barcodes = c["barcodes"].cpu().numpy().view(np.uint64)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "output.mtx"), "w") as f:
+        f.write("%%MatrixMarket matrix coordinate integer general\n")
+        f.write("%d\t%d\t%d\n" % (len(barcodes), len(names), len(ent)))
+        for row, g, v in zip(ent["row"].tolist(), ent["ec"].tolist(), ent["value"].tolist()):   # (sorted by row, then gene: as the device leaves them)
+            f.write("%d\t%d\t%d\n" % (row + 1, g + 1, v))
+    with open(os.path.join(out_dir, "output.barcodes.txt"), "w") as f:
+        for b in barcodes.tolist():
+            f.write("".join("ACGT"[(b >> (2 * (bclen - 1 - i))) & 3] for i in range(bclen)) + "\n")
+    with open(os.path.join(out_dir, "output.genes.txt"), "w") as f:
+        for g in names:
+            f.write(g + "\n")
+    out = {k: c["stats"][k] for k in GENE_KEYS}
+    with open(os.path.join(out_dir, "count.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m kallisto_amd.bus_sc", description="BUS records of a barcode / UMI technology on the GPU (a driver for moderate inputs)")
     ap.add_argument("-x", "--technology", required=True)
@@ -277,6 +326,8 @@ def main(argv=None):
     ap.add_argument("--union", action="store_true")
     ap.add_argument("--bus-per-read", action="store_true")
     ap.add_argument("--count", action="store_true", help="also write the barcodes x classes matrix of the records into <output-dir>/counts")
+    ap.add_argument("--genecounts", action="store_true", help="also write the barcodes x genes matrix of the records into <output-dir>/genes (needs -g)")
+    ap.add_argument("-g", "--genemap", metavar="FILE", help="transcripts-to-genes file of --genecounts: transcript, gene[, common name] per line")
     ap.add_argument("-w", "--whitelist", metavar="FILE", help="correct the records' barcodes against this list (one barcode per line, plain or gzip): what `bustools correct` does")
     ap.add_argument("--unit-records", type=int, default=UNIT_RECORDS, help=argparse.SUPPRESS)
     ap.add_argument("--merge-records", type=int, default=MERGE_RECORDS, help=argparse.SUPPRESS)
@@ -284,7 +335,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     try:
         info = run(a.technology, a.index, a.output_dir, a.files, a.strand, a.no_jump, a.union, a.bus_per_read, a.unit_records, count=a.count, merge_records=a.merge_records, whitelist=a.whitelist,
-                   call="python -m kallisto_amd.bus_sc " + " ".join(sys.argv[1:] if argv is None else argv))
+                   genecounts=a.genecounts, genemap=a.genemap, call="python -m kallisto_amd.bus_sc " + " ".join(sys.argv[1:] if argv is None else argv))
     except A.KallistoAmdError as e:
         print("Error:", e, file=sys.stderr)
         return 1

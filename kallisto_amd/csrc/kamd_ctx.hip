@@ -164,6 +164,8 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   for (hipEvent_t e : c->bus_ev) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->bcor_ev) if (e) (void)hipEventDestroy(e);
   whitelists_free_all(c);
+  for (hipEvent_t e : c->bgen_ev) if (e) (void)hipEventDestroy(e);
+  gene_tables_free_all(c);
   if (c->ev_ab0) (void)hipEventDestroy(c->ev_ab0);
   if (c->ev_ab1) (void)hipEventDestroy(c->ev_ab1);
   if (c->em_stream) (void)hipStreamDestroy(c->em_stream);
@@ -203,7 +205,8 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
                   &c->pt_ck_a, &c->fq_tiles, &c->fq_nlpos[0], &c->fq_nlpos[1], &c->fq_recs, &c->fq_res, &c->fq_words, &c->fq_len, &c->aa_frames, &c->aa_flen, &c->aa_scratch, &c->aa_offlist, &c->aa_ctr, &c->inf_members, &c->inf_res, &c->txt_counts, &c->txt_res,
                   &c->rec_table, &c->rec_scratch, &c->rec_big_scratch, &c->rec_big_items, &c->rec_ctr, &c->bus_blk, &c->bus_ctr,
                   &c->bsort_b, &c->bsort_hist, &c->bsort_tot, &c->bsort_sum, &c->bsort_ctr, &c->bcnt_units, &c->bcnt_gstart, &c->bcnt_mark, &c->bcnt_blk,
-                  &c->bcor_status, &c->bcor_miss, &c->bcor_fix, &c->bcor_ctr})
+                  &c->bcor_status, &c->bcor_miss, &c->bcor_fix, &c->bcor_ctr,
+                  &c->bgen_blk, &c->bgen_ctr, &c->bgen_gene, &c->bgen_list, &c->bgen_rows})
     b->release();
   delete c;
 }

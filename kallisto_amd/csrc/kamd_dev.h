@@ -19,6 +19,9 @@
 //                    groups (kamd_bus_count); per-record rules in kamd_bussort.h, the scan the bus units share in kamd_bus_scan.h
 //   kamd_buscorrect.hip barcode whitelists: the membership table built on the device (kamd_bus_whitelist_create) and the correction of a batch's
 //                    records against it (kamd_bus_correct); the table's rules and the rule of the correction in kamd_buscorrect.h
+//   kamd_busgenes.hip BUS records -> cells x genes: the gene lists of the classes built on the device (kamd_bus_genes_create) and the count that gives
+//                    every group of records the one gene its classes share (kamd_bus_count_genes); lists and rule in kamd_busgenes.h, what it shares
+//                    with kamd_bussort.hip in kamd_bussort_dev.h
 // The per-item semantics live in kamd_core.h (shared with the CPU emulation used by the tests).
 #pragma once
 
@@ -370,6 +373,11 @@ struct kamd_ctx {
   std::vector<struct kamd_bus_whitelist*> whitelists;
   DBuf bcor_status, bcor_miss, bcor_fix, bcor_ctr;
   hipEvent_t bcor_ev[2] = {nullptr, nullptr};
+  // BUS records -> cells x genes (kamd_busgenes.hip): the gene tables of this context (freed with it); of a kamd_bus_count_genes call the block counts,
+  // the counters, the gene of every group, the groups a wavefront settles, the rows until the call is known to succeed; the events around the resolve step
+  std::vector<struct kamd_bus_genes*> gene_tables;
+  DBuf bgen_blk, bgen_ctr, bgen_gene, bgen_list, bgen_rows;
+  hipEvent_t bgen_ev[2] = {nullptr, nullptr};
   std::vector<struct kamd_comm*> comms;   // communicators bound to this context (detached by kamd_ctx_destroy, so that either may go first)
 };
 
@@ -382,6 +390,8 @@ void apply_tuning(kamd_ctx* c);
 void comm_detach_all(kamd_ctx* c);
 // kamd_buscorrect.hip
 void whitelists_free_all(kamd_ctx* c);
+// kamd_busgenes.hip
+void gene_tables_free_all(kamd_ctx* c);
 // kamd_ixbuild.hip
 int index_build_device(kamd_ctx* c, const kamd_index* hix, const kamd_index_view& v, DevIndex* d, kamd_table_info* info);
 // kamd_ec.hip

@@ -125,7 +125,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 13
+#define KAMD_ABI_VERSION 14
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -219,6 +219,18 @@ typedef struct {
                                   taken on the host -- a path real reads hardly ever reach.  The scratch stays sized for 64 entries */
   int32_t fld_first_chunk;     /* test hook, fragment-length sample: items of the first prefix kamd_fld_prefetch / kamd_fld_from_batch look at
                                   (64..1048576; default 1048576); later prefixes are sized from the rate of qualifying pairs seen so far */
+  int32_t classify_counts_short; /* 1 (default) = k_classify counts the SHORT tuple records (two sets, or three whose ids fit short_id_bits) into the table of
+                                  distinct tuples itself -- such a tuple is its own exact tag, one word claimed and compared with atomics -- and only the other
+                                  tuple records wait for the absorption pass (plain paired / single-end runs: no positional filter, no --union, no
+                                  kamd_ec_track_order), and k_classify lists the items it leaves so that the pass reads those records alone; 3 = the same
+                                  without the list (the pass walks every slot of the batch, as it always did: for comparisons); 2 = every tuple record
+                                  waits for the absorption pass */
+  int32_t short_id_bits;       /* bits per id of a three-set exact tag (4..20; default 20: three ids below 2^20).  Part of every tag in the table: a new value
+                                  takes effect when the table of distinct tuples is empty (kamd_ec_reset).  Smaller values are for tests -- exact and hashed
+                                  three-set tuples in one small table */
+  int32_t tup_max_probe;       /* test hook: slots a tuple record tries before it goes to the fail list and the table grows (1..64; default 64) */
+  int32_t classify_max_blocks; /* test hook: at most this many persistent blocks of k_classify (-1 = as many as are resident at once, the default), so that a
+                                  small batch gives a block several tiles */
 } kamd_tuning;
 int kamd_ctx_tune(kamd_ctx*, const kamd_tuning*);
 int kamd_ctx_get_tuning(const kamd_ctx*, kamd_tuning* out);
@@ -327,6 +339,10 @@ typedef struct {
   uint64_t n_text_hits;     /* probes answered from the unitig text instead of the table */
   uint64_t n_wave_iters;    /* kernel A: loop trips summed over the wavefronts ... */
   uint64_t n_lane_iters;    /* ... and lanes that issued a probe in them: n_lane_iters / (64 n_wave_iters) = lane utilisation */
+  uint64_t n_classify_counted;  /* tuple records k_classify counted into the table of distinct tuples itself (kamd_tuning::classify_counts_short; 0 where
+                                   that path does not run) */
+  uint64_t n_three_exact;   /* three-set tuple records k_classify saw on that path whose ids fit short_id_bits (exact tag) ... */
+  uint64_t n_three_hashed;  /* ... and those with an id too wide (hash form, left to the absorption pass) */
 } kamd_align_stats;
 int kamd_align_stats_get(kamd_ctx*, kamd_align_stats* out);
 

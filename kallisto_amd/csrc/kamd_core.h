@@ -338,6 +338,74 @@ KAMD_HD void eclist_add(EcList& l, uint32_t ec_flags) {   // sorted by id; flags
   ++l.n;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// the tag word of a tuple record [cnt, m, e0 .. e(m-1)] in the table of distinct tuples (kamd_ec.hip)
+// ---------------------------------------------------------------------------------------------------------------
+// hash of n record words (the de-duplication's hash: never 0)
+KAMD_HD uint64_t rec_hash(const uint32_t* w, uint32_t n, uint64_t seed) {
+  uint64_t h = mix64(seed ^ (0x9e3779b97f4a7c15ULL * (n + 1)));
+  if (n > 64) {
+    // long records (candidate sets of thousands of transcripts): four interleaved chains -- one chain is 3 500 dependent multiplies for a poly-A
+    // class, and the thread's wavefront waits for it (k_rec_dedup 9.8 ms per 30 M stress pairs).  A record takes this form by its length alone.
+    uint64_t h0 = h, h1 = h ^ 0x9e3779b97f4a7c15ULL, h2 = h ^ 0xc2b2ae3d27d4eb4fULL, h3 = h ^ 0x165667b19e3779f9ULL;
+    uint32_t i = 0;
+    for (; i + 4 <= n; i += 4) { h0 = mix64(h0 ^ w[i]); h1 = mix64(h1 ^ w[i + 1]); h2 = mix64(h2 ^ w[i + 2]); h3 = mix64(h3 ^ w[i + 3]); }
+    for (; i < n; i++) h0 = mix64(h0 ^ w[i]);
+    return mix64(mix64(h0 ^ (h1 + 1)) ^ mix64(h2 ^ (h3 + 3))) | 1ULL;
+  }
+  for (uint32_t i = 0; i < n; i++) h = mix64(h ^ w[i]);
+  return h | 1ULL;  // 0 is the empty tag
+}
+// Two forms of the tag word, told apart by bit 63:
+//   exact (bit 63 set)   a SHORT tuple -- two sets whose ids are below 2^31, or three whose ids are below 2^short_id_bits -- is its tag: the
+//                        sorted ids at a fixed width, bit 62 = "three sets".  Equal tags are equal tuples; nothing else has to be read.
+//   hash (bit 63 clear)  everything else: bits 32 .. 62 of the record's hash; the caller puts where the owner's record lies into the low
+//                        half, and equality is settled by reading that record.
+// `start` is where the tuple's probe sequence begins (the caller reduces it to the table).  Every kernel that puts a tuple into the table
+// or looks one up takes word and start from here, so that a tuple lands in the same slot whichever kernel meets it.
+static const uint64_t TAG_EXACT = 1ULL << 63, TAG_THREE = 1ULL << 62, TAG_HASH_BITS = 0x7FFFFFFF00000000ULL;
+static const uint32_t SHORT_ID_BITS_MAX = 20;   // (three ids at 20 bits + the two flag bits fit the word; the default)
+struct TupleTag { uint64_t word, start; bool is_short; };
+// ... of a tuple of at most four sets held in registers (e[j] is only looked at for j < m)
+KAMD_HD TupleTag tuple_tag4(uint32_t m, uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, uint32_t short_id_bits) {
+  TupleTag t;
+  if (m == 2 && ((e0 | e1) >> 31) == 0) {
+    t.word = TAG_EXACT | ((uint64_t)e0 << 31) | e1; t.is_short = true;
+  } else if (m == 3 && ((e0 | e1 | e2) >> short_id_bits) == 0) {
+    t.word = TAG_EXACT | TAG_THREE | ((uint64_t)e0 << (2 * short_id_bits)) | ((uint64_t)e1 << short_id_bits) | e2; t.is_short = true;
+  } else {
+    uint64_t x = mix64(1ULL ^ (0x9e3779b97f4a7c15ULL * ((uint64_t)(m + 1) + 1)));   // rec_hash(words 1 .. m + 1 of the record, seed 1)
+    x = mix64(x ^ m);
+    if (m > 0) x = mix64(x ^ e0);
+    if (m > 1) x = mix64(x ^ e1);
+    if (m > 2) x = mix64(x ^ e2);
+    if (m > 3) x = mix64(x ^ e3);
+    x |= 1ULL;
+    t.word = x & TAG_HASH_BITS; t.start = x >> 1; t.is_short = false;
+    return t;
+  }
+  t.start = mix64(t.word) >> 1;
+  return t;
+}
+// ... of the record whose words 1 .. are rec[0] = m, rec[1 ..] = the sorted ids
+KAMD_HD TupleTag tuple_tag(const uint32_t* rec, uint32_t short_id_bits) {
+  const uint32_t m = rec[0];
+  if (m <= 4) return tuple_tag4(m, m > 0 ? rec[1] : 0u, m > 1 ? rec[2] : 0u, m > 2 ? rec[3] : 0u, m > 3 ? rec[4] : 0u, short_id_bits);
+  const uint64_t x = rec_hash(rec, m + 1, 1);
+  TupleTag t; t.word = x & TAG_HASH_BITS; t.start = x >> 1; t.is_short = false;
+  return t;
+}
+// the record of an exact tag, [m, e0 ..] (what k_tup_store rebuilds in the tuple store); returns m
+KAMD_HD uint32_t tuple_of_tag(uint64_t word, uint32_t short_id_bits, uint32_t* ids) {
+  if (word & TAG_THREE) {
+    const uint64_t mk = (1ULL << short_id_bits) - 1;
+    ids[0] = (uint32_t)((word >> (2 * short_id_bits)) & mk); ids[1] = (uint32_t)((word >> short_id_bits) & mk); ids[2] = (uint32_t)(word & mk);
+    return 3;
+  }
+  ids[0] = (uint32_t)((word >> 31) & 0x7FFFFFFFu); ids[1] = (uint32_t)(word & 0x7FFFFFFFu);
+  return 2;
+}
+
 struct MateInfo {
   int n_hits;        // v.size()
   int n_nonempty;    // != 0 when some hit carries a non-empty transcript set

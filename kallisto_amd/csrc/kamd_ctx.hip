@@ -10,6 +10,7 @@ void tuning_defaults(kamd_tuning* t) {
   t->em_fin_blocks = 1024; t->dedup_form = 2; t->align_chunks = -1; t->em_reg_slices = 1;
   t->em_hybrid = 1; t->overflow_second_pass = 1; t->em_giant_nnz = -1; t->em_blocked = 1;
   t->fld_list_cap = 64; t->fld_first_chunk = 1048576;
+  t->classify_counts_short = 1; t->short_id_bits = (int32_t)kamd::SHORT_ID_BITS_MAX; t->tup_max_probe = 64; t->classify_max_blocks = -1;
 }
 // 0 = keep; values outside a field's range are ignored
 void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
@@ -37,6 +38,10 @@ void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
   if (n.em_giant_nnz != 0) t->em_giant_nnz = n.em_giant_nnz < 0 ? -1 : std::max(n.em_giant_nnz, 8);
   if (n.fld_list_cap >= 1 && n.fld_list_cap <= 64) t->fld_list_cap = n.fld_list_cap;
   if (n.fld_first_chunk >= 64 && n.fld_first_chunk <= 1048576) t->fld_first_chunk = n.fld_first_chunk;
+  if (n.classify_counts_short >= 1 && n.classify_counts_short <= 3) t->classify_counts_short = n.classify_counts_short;
+  if (n.short_id_bits >= 4 && n.short_id_bits <= (int32_t)kamd::SHORT_ID_BITS_MAX) t->short_id_bits = n.short_id_bits;
+  if (n.tup_max_probe >= 1 && n.tup_max_probe <= 64) t->tup_max_probe = n.tup_max_probe;
+  if (n.classify_max_blocks != 0) t->classify_max_blocks = n.classify_max_blocks < 0 ? -1 : n.classify_max_blocks;
 }
 // experiments: the same knobs from ONE environment variable, read once when a context is created --
 //   KAMD_TUNE="em_form=streamed,em_graph=0,items_per_wave=512"   (field names of kamd_tuning; on/off fields take 1 / 0; em_form also by name)
@@ -54,7 +59,9 @@ void tuning_from_env(kamd_tuning* t) {
     {"em_split_len", &kamd_tuning::em_split_len, false}, {"dedup_form", &kamd_tuning::dedup_form, false}, {"align_chunks", &kamd_tuning::align_chunks, false},
     {"em_small_nnz", &kamd_tuning::em_small_nnz, false}, {"em_reg_slices", &kamd_tuning::em_reg_slices, true}, {"em_hybrid", &kamd_tuning::em_hybrid, true},
     {"overflow_second_pass", &kamd_tuning::overflow_second_pass, false}, {"em_giant_nnz", &kamd_tuning::em_giant_nnz, false}, {"em_blocked", &kamd_tuning::em_blocked, true},
-    {"fld_list_cap", &kamd_tuning::fld_list_cap, false}, {"fld_first_chunk", &kamd_tuning::fld_first_chunk, false}};
+    {"fld_list_cap", &kamd_tuning::fld_list_cap, false}, {"fld_first_chunk", &kamd_tuning::fld_first_chunk, false},
+    {"classify_counts_short", &kamd_tuning::classify_counts_short, false}, {"short_id_bits", &kamd_tuning::short_id_bits, false},
+    {"tup_max_probe", &kamd_tuning::tup_max_probe, false}, {"classify_max_blocks", &kamd_tuning::classify_max_blocks, false}};
   std::string all(e);
   for (size_t pos = 0; pos < all.size();) {
     size_t end = all.find(',', pos);
@@ -71,6 +78,7 @@ void tuning_from_env(kamd_tuning* t) {
       int32_t v = atoi(val.c_str());
       if (key == "em_form") v = val == "streamed" ? 1 : val == "csr" ? 2 : val == "local" ? 3 : v;
       if (key == "overflow_second_pass" && v == 0) v = 2;   // (1 = beside the absorption, 3 = after it, 0 / 2 = off)
+      if (key == "classify_counts_short" && v == 0) v = 2;  // (1 = on, with the list of what is left; 3 = on, without it; 0 / 2 = off)
       n.*(f.p) = f.onoff ? (v != 0 ? 1 : 2) : v;
     }
     if (!known) fprintf(stderr, "[kallisto_amd] KAMD_TUNE: unknown field '%s' ignored\n", key.c_str());
@@ -196,7 +204,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   if (c->sell_cache) sell_cache_free(c->sell_cache);
   for (void* p : c->index_allocs) (void)hipFree(p);
   for (DBuf* b : {&c->dense, &c->stream_buf, &c->rec_off, &c->overflow_items, &c->overflow_scratch, &c->state, &c->rec_slot,
-                  &c->retry, &c->ttable, &c->tstore, &c->stats_a, &c->list, &c->cand, &c->cand_off, &c->cand_slot, &c->ctable, &c->tup_bound, &c->tup_off, &c->tup_big, &c->raw2, &c->overflow_left, &c->stats_b, &c->clist, &c->sizes, &c->explicit_items,
+                  &c->retry, &c->ttable, &c->tstore, &c->todo, &c->todo_cnt, &c->stats_a, &c->list, &c->cand, &c->cand_off, &c->cand_slot, &c->ctable, &c->tup_bound, &c->tup_off, &c->tup_big, &c->raw2, &c->overflow_left, &c->stats_b, &c->clist, &c->sizes, &c->explicit_items,
                   &c->explicit_items_big, &c->exp_stream, &c->exp_off, &c->exp_scratch, &c->bs_cp, &c->bs_samp, &c->raw, &c->dense_first, &c->exp_key, &c->cand_key, &c->ec_first, &c->pm_a, &c->pm_b, &c->pm_rank, &c->eml_tmp, &c->ems_tmp, &c->ems_plan, &c->ems_maps, &c->fld_tl, &c->fld_card, &c->fld_scratch, &c->fld_items, &c->fld_cand,
                   &c->block_sums, &c->ec_off, &c->ec_ids, &c->ec_counts, &c->em_alpha, &c->em_next, &c->em_eff,
                   &c->em_state, &c->em_cn, &c->em_colcnt, &c->em_coloff, &c->em_colrow,

@@ -110,12 +110,18 @@ struct DevState {
   u64 n_big, n_huge;             // kamd_ec_finalize: distinct tuples whose smallest set has 17 .. 1024 / more than 1024 members (k_resolve_big's work lists)
   u64 n_sh_small, n_sh_long;     // ... an index with shades: tuples whose sets hold shades, by the size of members + shades (k_shade_extend's work lists)
   u64 shade_err;                 // k_shade_extend found a slot smaller than its own count of the shades needs (reported by kamd_ec_finalize)
+  u64 cs_counted;                // tuple records k_classify counted into the tuple table itself (short tuples: exact tags)
+  u64 cs_three_exact, cs_three_hash;   // k_classify's three-set tuple records by the form of their tag (exact: every id fits short_id_bits)
 };
 
 // counters of kernel A (their own struct: chunks of kernel A run on one stream while another copies DevState to and fro)
 struct DevStatsA { u64 probes, bucket_reads, raw_words, text_hits, wave_iters, lane_iters; };
 
 struct TSlot { u64 tag, owner, count, first; };  // first: smallest first-occurrence key of the merged records (candidate table)
+// the table of distinct tuples as a kernel of another unit sees it (k_classify counts the short tuples itself): absorb_prepare fills it in
+// todo / todo_cnt (optional): the items that are still tuple records afterwards, one segment of seg_cap entries per wavefront of the launch and the
+// number filled in each -- what the absorption pass then looks at instead of every slot
+struct TupleTarget { TSlot* table; u64 mask; u64* list; u32 max_probe, sbits; u32* todo; u32* todo_cnt; u32 n_segs, seg_cap; };
 
 // ------------------------------------------------------------------------------------------------------------------
 // wavefront helpers (64 lanes)
@@ -135,20 +141,7 @@ __device__ __forceinline__ u64 wave_sum64(u64 v) {
   return v;  // valid in lane 0
 }
 
-__device__ __forceinline__ u64 rec_hash(const u32* w, u32 n, u64 seed) {
-  u64 h = kamd::mix64(seed ^ (0x9e3779b97f4a7c15ULL * (n + 1)));
-  if (n > 64) {
-    // long records (candidate sets of thousands of transcripts): four interleaved chains -- one chain is 3 500 dependent multiplies for a poly-A
-    // class, and the thread's wavefront waits for it (k_rec_dedup 9.8 ms per 30 M stress pairs).  A record takes this form by its length alone.
-    u64 h0 = h, h1 = h ^ 0x9e3779b97f4a7c15ULL, h2 = h ^ 0xc2b2ae3d27d4eb4fULL, h3 = h ^ 0x165667b19e3779f9ULL;
-    u32 i = 0;
-    for (; i + 4 <= n; i += 4) { h0 = kamd::mix64(h0 ^ w[i]); h1 = kamd::mix64(h1 ^ w[i + 1]); h2 = kamd::mix64(h2 ^ w[i + 2]); h3 = kamd::mix64(h3 ^ w[i + 3]); }
-    for (; i < n; i++) h0 = kamd::mix64(h0 ^ w[i]);
-    return kamd::mix64(kamd::mix64(h0 ^ (h1 + 1)) ^ kamd::mix64(h2 ^ (h3 + 3))) | 1ULL;
-  }
-  for (u32 i = 0; i < n; i++) h = kamd::mix64(h ^ w[i]);
-  return h | 1ULL;  // 0 is the empty tag
-}
+__device__ __forceinline__ u64 rec_hash(const u32* w, u32 n, u64 seed) { return kamd::rec_hash(w, n, seed); }   // (kamd_core.h, beside the tuple tag)
 
 __device__ __forceinline__ bool onlisted(const u32* bits, u32 t) { return (bits[t >> 5] >> (t & 31)) & 1u; }
 __device__ __forceinline__ bool set_contains(const u32* ids, u32 n, u32 x) {
@@ -311,10 +304,13 @@ struct kamd_ctx {
   DevState* state_pin = nullptr;   // pinned staging of the read-backs (sync_state)
   u64 tcap = 0, ccap = 0;        // slots of the tuple table (persistent over the batches of a run) / the candidate table
   DBuf tstore;                   // the tuple store: the distinct tuple records of the run, compact
+  DBuf todo, todo_cnt;           // k_classify's list of the items it left to the absorption pass (TupleTarget)
   bool ttable_clean = false;     // the tuple table holds no entries (just initialised)
   u64 recs_total = 0;            // records (items) of the batches absorbed so far: first-occurrence keys
   u64 multi_before = 0;          // st_multi before the current batch
   u64 n_distinct_tuples = 0;
+  u32 short_bits = kamd::SHORT_ID_BITS_MAX;   // width of a three-set exact tag's ids in the tuple table (tune.short_id_bits, latched while the table is empty)
+  u64 ab_bound = 0, ab_tl_before = 0;         // absorb_prepare -> absorb_rest: records the lists are sized for, owners before the batch
   float last_absorb_ms = 0.f; hipEvent_t ev_ab0 = nullptr, ev_ab1 = nullptr;
   kamd_ec_result result{};
   bool finalized = false;
@@ -399,6 +395,9 @@ int exclusive_scan(kamd_ctx* c, const u32* sizes, u64 n, u64* out, u64* d_total)
 int tuples_clear(kamd_ctx* c);
 int absorb_tuples(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 batch_words, u64 key_base, u64 n_tuple_bound,
                   const u64* first_idx = nullptr, u32 fixed_stride = 0, u64 item0 = 0);
+int absorb_prepare(kamd_ctx* c, u64 bound, TupleTarget* target, bool in_absorb);
+int absorb_rest(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 batch_words, u64 key_base, const u64* first_idx, u32 fixed_stride,
+                u64 item0, const TupleTarget* todo, bool started);
 template <class T>
 int upload(kamd_ctx* c, const T* host, size_t n, const T** dev) {
   void* p = nullptr;

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(BLOCK) void k_rec_dedup(const u32* __restrict__ str
 constexpr u64 TAG_LOCAL = 0x80000000ULL;   // the tag's offset refers to the batch's stream (the record is not in the store yet)
 __global__ __launch_bounds__(BLOCK) void k_tup_absorb(const u32* __restrict__ batch, const u32* __restrict__ store, const u64* __restrict__ rec_off,
                                                       const u64* __restrict__ idx, u64 n, TSlot* table, u64 mask, u64* list, u64 key_base, int track,
-                                                      u32 max_probe, u64* fail, DevState* st, u32 fixed_stride = 0, u64 item0 = 0) {
+                                                      u32 max_probe, u64* fail, DevState* st, u32 sbits, u32 fixed_stride = 0, u64 item0 = 0) {
   __shared__ u32 blk_n, blk_words; __shared__ u64 blk_base;
   if (threadIdx.x == 0) { blk_n = 0; blk_words = 0; }
   __syncthreads();
@@ -136,9 +136,9 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb(const u32* __restrict__ ba
     const u64 off = fixed_stride ? (item0 + r) * (u64)fixed_stride : rec_off[r];
     if (off != ~0ULL && batch[off] != 0u) {
       m = batch[off + 1];
-      const u64 h = rec_hash(batch + off + 1, m + 1, 1);
-      const u64 mine = (h & 0xFFFFFFFF00000000ULL) | TAG_LOCAL | (off + 1);   // off + 1 < 2^31 (checked by the host)
-      s = (h >> 1) & mask;
+      const kamd::TupleTag tg = kamd::tuple_tag(batch + off + 1, sbits);
+      const u64 mine = tg.is_short ? tg.word : (tg.word | TAG_LOCAL | (off + 1));   // off + 1 < 2^31 (checked by the host)
+      s = tg.start & mask;
       bool placed = false;
       for (u32 probes = 0; probes < max_probe; probes++) {
         // nine records in ten find their tuple already in the table: a plain load sees the tag without the trip to the memory side
@@ -147,7 +147,8 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb(const u32* __restrict__ ba
         u64 old = table[s].tag;
         if (old == 0ULL) old = atomicCAS(&table[s].tag, 0ULL, mine);
         if (old == 0ULL) { is_owner = true; table[s].owner = off; placed = true; break; }
-        if ((old >> 32) == (mine >> 32)) {
+        if (tg.is_short) { if (old == mine) { placed = true; break; } }   // (an exact tag: equal words are equal tuples)
+        else if ((old >> 32) == (mine >> 32)) {
           const u32* o = ((old & TAG_LOCAL) ? batch : store) + ((old & 0x7FFFFFFFULL) - 1);
           bool same = o[1] == m;
           for (u32 j = 0; same && j < m; j++) same = o[2 + j] == batch[off + 2 + j];
@@ -174,19 +175,32 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb(const u32* __restrict__ ba
 // the four owner reads are each in flight together --, everything else (an empty slot to claim, a collision, a tuple of more than four
 // sets) takes k_tup_absorb's loop, one record at a time, afterwards.  Thread t takes records t, t + T, t + 2T, t + 3T (T = threads of
 // the launch): every one of the four rounds reads consecutive slots.
+// With a list of the items to look at (`todo`: k_classify, which counts the short tuples itself, lists what is left -- one segment of seg_cap entries
+// per wavefront of its launch, todo_cnt[segment] of them filled) block (s, j) takes entries j x 256 x ABS_Q .. of segment s instead: the records that
+// are not tuple records any more are never read.
 constexpr int ABS_Q = 4;
 __global__ __launch_bounds__(BLOCK) void k_tup_absorb4(const u32* __restrict__ batch, const u32* __restrict__ store, u64 n, TSlot* table, u64 mask, u64* list,
-                                                       u64 key_base, int track, u32 max_probe, u64* fail, DevState* st, u32 stride, u64 item0) {
+                                                       u64 key_base, int track, u32 max_probe, u64* fail, DevState* st, u32 sbits, u32 stride, u64 item0,
+                                                       const u32* __restrict__ todo, const u32* __restrict__ todo_cnt, u32 seg_cap) {
   __shared__ u32 blk_n, blk_words; __shared__ u64 blk_base;
+  u32 seg_n = 0;
+  if (todo) { seg_n = todo_cnt[blockIdx.x]; if ((u64)blockIdx.y * (BLOCK * ABS_Q) >= seg_n) return; }   // (the whole block)
   if (threadIdx.x == 0) { blk_n = 0; blk_words = 0; }
   __syncthreads();
   const u64 T = (u64)gridDim.x * blockDim.x;
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  u64 off[ABS_Q]; u32 w[ABS_Q][6]; bool live[ABS_Q], slow[ABS_Q];
+  u64 rr[ABS_Q], off[ABS_Q]; u32 w[ABS_Q][6]; bool live[ABS_Q], slow[ABS_Q];
 #pragma unroll
   for (int q = 0; q < ABS_Q; q++) {
-    const u64 r = i + (u64)q * T;
+    u64 r = i + (u64)q * T;
     live[q] = r < n;
+    if (todo) {
+      const u32 e = blockIdx.y * (u32)(BLOCK * ABS_Q) + (u32)q * BLOCK + threadIdx.x;
+      live[q] = e < seg_n;
+      r = live[q] ? (u64)todo[(u64)blockIdx.x * seg_cap + e] : 0ULL;
+      live[q] = live[q] && r < n;
+    }
+    rr[q] = r;
     off[q] = (item0 + (live[q] ? r : 0)) * (u64)stride;
     const uint2* p = reinterpret_cast<const uint2*>(batch + off[q]);   // (slots of 14 words: 8-byte aligned)
     const uint2 a = live[q] ? p[0] : make_uint2(0u, 0u);
@@ -195,36 +209,34 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb4(const u32* __restrict__ b
     live[q] = live[q] && a.x != 0u;
     slow[q] = live[q] && a.y > 4u;
   }
-  u64 h[ABS_Q], sl[ABS_Q], old[ABS_Q];
+  u64 h[ABS_Q], sl[ABS_Q], old[ABS_Q]; bool sh[ABS_Q];
 #pragma unroll
   for (int q = 0; q < ABS_Q; q++) {
-    const u32 m = w[q][1];
-    u64 x = kamd::mix64(1ULL ^ (0x9e3779b97f4a7c15ULL * ((u64)(m + 1) + 1)));   // rec_hash(words 1 .. m + 1, seed 1)
-    x = kamd::mix64(x ^ m);
-#pragma unroll
-    for (int j = 0; j < 4; j++) if ((u32)j < m) x = kamd::mix64(x ^ w[q][2 + j]);
-    h[q] = x | 1ULL;
-    sl[q] = (h[q] >> 1) & mask;
+    const kamd::TupleTag tg = kamd::tuple_tag4(w[q][1], w[q][2], w[q][3], w[q][4], w[q][5], sbits);   // (only used for m <= 4)
+    h[q] = tg.word; sh[q] = tg.is_short;
+    sl[q] = tg.start & mask;
     old[q] = (live[q] && !slow[q]) ? table[sl[q]].tag : 0ULL;
   }
   u32 ow[ABS_Q][5]; bool cand[ABS_Q];
 #pragma unroll
   for (int q = 0; q < ABS_Q; q++) {
-    cand[q] = live[q] && !slow[q] && old[q] != 0ULL && (old[q] >> 32) == (h[q] >> 32);
+    // (an exact tag settles the matter by itself: the owner's record is only read for the hash form)
+    cand[q] = live[q] && !slow[q] && old[q] != 0ULL && (sh[q] ? old[q] == h[q] : (old[q] >> 32) == (h[q] >> 32));
+    const bool rd = cand[q] && !sh[q];
     const u32* o = ((old[q] & TAG_LOCAL) ? batch : store) + ((old[q] & 0x7FFFFFFFULL) - 1);
     const u32 m = w[q][1];
 #pragma unroll
-    for (int j = 0; j < 5; j++) ow[q][j] = (cand[q] && (u32)j <= m) ? o[1 + j] : 0u;   // the owner's m and its first four sets
+    for (int j = 0; j < 5; j++) ow[q][j] = (rd && (u32)j <= m) ? o[1 + j] : 0u;   // the owner's m and its first four sets
   }
 #pragma unroll
   for (int q = 0; q < ABS_Q; q++) {
     if (!live[q] || slow[q]) continue;
-    bool same = cand[q] && ow[q][0] == w[q][1];
+    bool same = cand[q] && (sh[q] || ow[q][0] == w[q][1]);
 #pragma unroll
-    for (int j = 0; j < 4; j++) if ((u32)j < w[q][1]) same = same && ow[q][1 + j] == w[q][2 + j];
+    for (int j = 0; j < 4; j++) if (!sh[q] && (u32)j < w[q][1]) same = same && ow[q][1 + j] == w[q][2 + j];
     if (same) {
       atomicAdd(&table[sl[q]].count, (u64)w[q][0]);
-      if (track & 1) atomicMin(&table[sl[q]].first, key_base + i + (u64)q * T);
+      if (track & 1) atomicMin(&table[sl[q]].first, key_base + rr[q]);
     } else slow[q] = true;
   }
   // the rest: k_tup_absorb's loop
@@ -233,17 +245,18 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb4(const u32* __restrict__ b
   for (int q = 0; q < ABS_Q; q++) {
     is_owner[q] = false; my[q] = 0; own_s[q] = 0;
     if (!slow[q]) continue;
-    const u64 r = i + (u64)q * T, o = off[q];
+    const u64 r = rr[q], o = off[q];
     const u32 m = batch[o + 1];
-    const u64 hh = rec_hash(batch + o + 1, m + 1, 1);
-    const u64 mine = (hh & 0xFFFFFFFF00000000ULL) | TAG_LOCAL | (o + 1);   // o + 1 < 2^31 (checked by the host)
-    u64 s = (hh >> 1) & mask;
+    const kamd::TupleTag tg = kamd::tuple_tag(batch + o + 1, sbits);
+    const u64 mine = tg.is_short ? tg.word : (tg.word | TAG_LOCAL | (o + 1));   // o + 1 < 2^31 (checked by the host)
+    u64 s = tg.start & mask;
     bool placed = false;
     for (u32 probes = 0; probes < max_probe; probes++) {
       u64 od = table[s].tag;
       if (od == 0ULL) od = atomicCAS(&table[s].tag, 0ULL, mine);
       if (od == 0ULL) { is_owner[q] = true; table[s].owner = o; placed = true; break; }
-      if ((od >> 32) == (mine >> 32)) {
+      if (tg.is_short) { if (od == mine) { placed = true; break; } }
+      else if ((od >> 32) == (mine >> 32)) {
         const u32* ob = ((od & TAG_LOCAL) ? batch : store) + ((od & 0x7FFFFFFFULL) - 1);
         bool same = ob[1] == m;
         for (u32 j = 0; same && j < m; j++) same = ob[2 + j] == batch[o + 2 + j];
@@ -263,13 +276,18 @@ __global__ __launch_bounds__(BLOCK) void k_tup_absorb4(const u32* __restrict__ b
 #pragma unroll
   for (int q = 0; q < ABS_Q; q++) if (is_owner[q]) list[blk_base + my[q]] = own_s[q];
 }
-// the records that opened a slot in the last k_tup_absorb move from the batch's stream into the store
+// the records that opened a slot in the last k_tup_absorb (or in k_classify, which counts the short tuples itself) move into the store: from the
+// batch's stream, or -- a slot with an exact tag, whose owner may have left no record behind -- rebuilt from the tag
 __global__ __launch_bounds__(BLOCK) void k_tup_store(const u32* __restrict__ batch, u32* store, TSlot* table, u64* list, u64 first_new,
-                                                     u64 n_new, DevState* st) {
+                                                     u64 n_new, DevState* st, u32 sbits) {
   __shared__ u32 wsum[BLOCK / 64]; __shared__ u64 blk_base;
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-  u64 s = 0, off = 0; u32 need = 0;
-  if (i < n_new) { s = list[first_new + i] & 0xFFFFFFFFULL; off = table[s].owner; need = batch[off + 1] + 2u; }
+  u64 s = 0, off = 0, tag = 0; u32 need = 0;
+  if (i < n_new) {
+    s = list[first_new + i] & 0xFFFFFFFFULL; tag = table[s].tag;
+    if (tag & kamd::TAG_EXACT) need = ((tag & kamd::TAG_THREE) ? 3u : 2u) + 2u;
+    else { off = table[s].owner; need = batch[off + 1] + 2u; }
+  }
   const u32 incl = wave_incl_scan(need);
   if (lane_id() == 63) wsum[threadIdx.x >> 6] = incl;
   __syncthreads();
@@ -279,22 +297,29 @@ __global__ __launch_bounds__(BLOCK) void k_tup_store(const u32* __restrict__ bat
   u32 before = 0;
   for (u32 j = 0; j < (threadIdx.x >> 6); j++) before += wsum[j];
   const u64 dst = blk_base + before + incl - need;
-  for (u32 j = 0; j < need; j++) store[dst + j] = batch[off + j];
-  table[s].owner = dst;
-  table[s].tag = (table[s].tag & 0xFFFFFFFF00000000ULL) | (dst + 1);   // (dst + 1 < 2^31: checked by the host)
+  if (tag & kamd::TAG_EXACT) {
+    u32 ids[3] = {0u, 0u, 0u};
+    const u32 m = kamd::tuple_of_tag(tag, sbits, ids);
+    store[dst] = 1u; store[dst + 1] = m; store[dst + 2] = ids[0]; store[dst + 3] = ids[1];
+    if (m == 3) store[dst + 4] = ids[2];
+    table[s].owner = dst;   // (the tag stays: it names no place)
+  } else {
+    for (u32 j = 0; j < need; j++) store[dst + j] = batch[off + j];
+    table[s].owner = dst;
+    table[s].tag = (tag & 0xFFFFFFFF00000000ULL) | (dst + 1);   // (dst + 1 < 2^31: checked by the host)
+  }
   // the list entry carries the record's place in the store beside the slot: the kernels that walk the distinct tuples (k_bound_tuples,
   // k_resolve) start on the record at once instead of going list -> slot -> record, one dependent random read less per tuple
   list[first_new + i] = s | (dst << 32);
 }
 // a larger table: every distinct tuple (all of them in the store by now) takes a slot of the new one, the list follows
-__global__ void k_tup_rehash(const u32* __restrict__ store, const TSlot* __restrict__ old, TSlot* nu, u64 mask, u64* list, u64 n) {
+__global__ void k_tup_rehash(const u32* __restrict__ store, const TSlot* __restrict__ old, TSlot* nu, u64 mask, u64* list, u64 n, u32 sbits) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const TSlot o = old[list[i] & 0xFFFFFFFFULL];
-  const u32 m = store[o.owner + 1];
-  const u64 h = rec_hash(store + o.owner + 1, m + 1, 1);
-  const u64 tag = (h & 0xFFFFFFFF00000000ULL) | (o.owner + 1);
-  u64 s = (h >> 1) & mask;
+  const kamd::TupleTag tg = kamd::tuple_tag(store + o.owner + 1, sbits);
+  const u64 tag = tg.is_short ? tg.word : (tg.word | (o.owner + 1));
+  u64 s = tg.start & mask;
   while (atomicCAS(&nu[s].tag, 0ULL, tag) != 0ULL) s = (s + 1) & mask;
   nu[s].owner = o.owner; nu[s].count = o.count; nu[s].first = o.first;
   list[i] = s | (o.owner << 32);
@@ -1086,7 +1111,7 @@ int tuples_resize(kamd_ctx* c, u64 cap) {
   if (int rc = nu.ensure(cap * sizeof(TSlot), 0, c->stream)) return rc;
   hipLaunchKernelGGL(k_table_init, dim3(grid_for(cap, BLOCK)), dim3(BLOCK), 0, c->stream, nu.as<TSlot>(), cap);
   if (n) hipLaunchKernelGGL(k_tup_rehash, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, c->stream, (const u32*)c->tstore.as<u32>(), (const TSlot*)c->ttable.as<TSlot>(),
-                            nu.as<TSlot>(), cap - 1, c->list.as<u64>(), n);
+                            nu.as<TSlot>(), cap - 1, c->list.as<u64>(), n, c->short_bits);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(c->stream));
   c->ttable.release();
@@ -1098,43 +1123,84 @@ int tuples_resize(kamd_ctx* c, u64 cap) {
 // 21.7 M tuple records collapse to 2.0 M distinct tuples; a table for every record would be gigabytes to clear and to miss in),
 // is kept at most half full, and a record that finds no slot within 64 probes makes it grow before that record is tried again.
 // first_idx (device, optional): the records to look at are rec_off[first_idx[0 .. n-1]] instead of rec_off[0 .. n-1]
-int absorb_tuples(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 batch_words, u64 key_base, u64 n_tuple_bound,
-                  const u64* first_idx, u32 fixed_stride, u64 item0) {
-  if (n == 0) return 0;
-  if (batch_words >= 0x7FFFFFF0ULL) return kamd::fail(-1, "kamd_pseudoalign: the record stream of one batch must stay below 2^31 words (use smaller batches)");
-  DevState* dst = (DevState*)c->state.p;
+// Two steps.  absorb_prepare: the table, the owners' list and the fail lists for at most `bound` records, the counters of a round on the device --
+// after it a kernel of another unit (k_classify) may count short tuples into the table through *target.  absorb_rest: the batch's records, the
+// new owners (whoever made them) into the store, retries after a growth.  absorb_tuples is the two in one call.
+// in_absorb: the caller has recorded ev_ab0 and will call absorb_rest(..., started = true) -- everything here is then inside the absorption's time, as
+// it always was; otherwise (k_classify comes in between) only a table set-up or growth is timed here, and the size checks and the push of the counters
+// (host work and one small copy) fall before k_classify's events
+int absorb_prepare(kamd_ctx* c, u64 bound, TupleTarget* target, bool in_absorb) {
   if (!c->ev_ab0) { HIPC(hipEventCreate(&c->ev_ab0)); HIPC(hipEventCreate(&c->ev_ab1)); }
-  HIPC(hipEventRecord(c->ev_ab0, c->stream));
-  const u64 bound = std::min(n, n_tuple_bound);
+  if (in_absorb) HIPC(hipEventRecord(c->ev_ab0, c->stream));
+  // (the width of a three-set exact tag is part of every tag in the table: a new value waits for an empty table)
+  if (c->host_state.tl_n == 0) c->short_bits = (u32)c->tune.short_id_bits;
   u64 want = pow2_at_least(std::max<u64>(bound / 4, 2 * c->host_state.tl_n) + 16);
+  bool timed = false;
   if (c->tcap == 0) {
+    if (!in_absorb) { HIPC(hipEventRecord(c->ev_ab0, c->stream)); timed = true; }
     c->tcap = want;
     if (int rc = c->ttable.ensure(c->tcap * sizeof(TSlot), 0, c->stream)) return rc;
     hipLaunchKernelGGL(k_table_init, dim3(grid_for(c->tcap, BLOCK)), dim3(BLOCK), 0, c->stream, c->ttable.as<TSlot>(), c->tcap);
     c->ttable_clean = true;
   } else if (2 * c->host_state.tl_n + 16 > c->tcap) {
+    if (!in_absorb) { HIPC(hipEventRecord(c->ev_ab0, c->stream)); timed = true; }
     if (int rc = tuples_resize(c, pow2_at_least(4 * c->host_state.tl_n + 16))) return rc;
+  }
+  if (timed) {   // (the table's set-up belongs to the absorption's time, as it always did)
+    HIPC(hipEventRecord(c->ev_ab1, c->stream));
+    HIPC(hipEventSynchronize(c->ev_ab1));
+    float ms = 0.f;
+    HIPC(hipEventElapsedTime(&ms, c->ev_ab0, c->ev_ab1));
+    c->last_absorb_ms += ms;
   }
   if (int rc = c->list.ensure((c->host_state.tl_n + bound + 1) * sizeof(u64), c->host_state.tl_n * sizeof(u64), c->stream)) return rc;
   if (int rc = c->retry.ensure(2 * (bound + 1) * sizeof(u64), 0, c->stream)) return rc;
+  c->ab_bound = bound; c->ab_tl_before = c->host_state.tl_n;
+  c->host_state.tl_fail = 0; c->host_state.bound_words = 0;
+  if (int rc = push_state(c)) return rc;
+  if (target) {
+    target->table = c->ttable.as<TSlot>(); target->mask = c->tcap - 1; target->list = c->list.as<u64>();
+    target->max_probe = (u32)c->tune.tup_max_probe; target->sbits = c->short_bits;
+    target->todo = nullptr; target->todo_cnt = nullptr; target->n_segs = 0; target->seg_cap = 0;
+    c->ttable_clean = false;
+  }
+  return 0;
+}
+// prepared: absorb_prepare ran for this batch and the host's copy of the counters is the device's (the owners made since, their words and the
+// records that found no slot are in it)
+// todo (optional; with fixed_stride, without first_idx): the items to look at, as k_tup_absorb4 takes them
+int absorb_rest(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 batch_words, u64 key_base, const u64* first_idx, u32 fixed_stride,
+                u64 item0, const TupleTarget* todo, bool started) {
+  if (batch_words >= 0x7FFFFFF0ULL) return kamd::fail(-1, "kamd_pseudoalign: the record stream of one batch must stay below 2^31 words (use smaller batches)");
+  DevState* dst = (DevState*)c->state.p;
+  if (!started) HIPC(hipEventRecord(c->ev_ab0, c->stream));
+  const u64 bound = c->ab_bound;
+  const u32 max_probe = (u32)c->tune.tup_max_probe, sbits = c->short_bits;
   u64* fail_a = c->retry.as<u64>();
   u64* fail_b = fail_a + bound + 1;
   const u64* idx = first_idx;
   u64 count = n;
   for (int round = 0; count; round++) {
     if (round > 40) return kamd::fail(-101, "absorb_tuples: the tuple table does not settle");
-    const u64 tl_before = c->host_state.tl_n;
-    c->host_state.tl_fail = 0; c->host_state.bound_words = 0;
-    if (int rc = push_state(c)) return rc;
+    u64 tl_before = c->ab_tl_before;
+    if (round > 0) {
+      tl_before = c->host_state.tl_n;
+      c->host_state.tl_fail = 0; c->host_state.bound_words = 0;
+      if (int rc = push_state(c)) return rc;
+    }
     // (the main pass of a batch -- kernel A's records in fixed slots of at least six words -- four records per thread; retries, overflow
     // items and gathered records one per thread)
-    if (!idx && fixed_stride >= 6 && (fixed_stride & 1) == 0)
-      hipLaunchKernelGGL(k_tup_absorb4, dim3(grid_for((count + ABS_Q - 1) / ABS_Q, BLOCK)), dim3(BLOCK), 0, c->stream, batch, (const u32*)c->tstore.as<u32>(), count,
-                         c->ttable.as<TSlot>(), c->tcap - 1, c->list.as<u64>(), key_base, c->track_order ? 1 : 0, 64u, fail_a, dst, fixed_stride, item0);
+    if (!idx && fixed_stride >= 6 && (fixed_stride & 1) == 0) {
+      const bool seg = todo && todo->todo && todo->n_segs;
+      const dim3 grid = seg ? dim3(todo->n_segs, grid_for(todo->seg_cap, BLOCK * ABS_Q)) : dim3(grid_for((count + ABS_Q - 1) / ABS_Q, BLOCK));
+      hipLaunchKernelGGL(k_tup_absorb4, grid, dim3(BLOCK), 0, c->stream, batch, (const u32*)c->tstore.as<u32>(), count,
+                         c->ttable.as<TSlot>(), c->tcap - 1, c->list.as<u64>(), key_base, c->track_order ? 1 : 0, max_probe, fail_a, dst, sbits, fixed_stride, item0,
+                         seg ? (const u32*)todo->todo : nullptr, seg ? (const u32*)todo->todo_cnt : nullptr, seg ? todo->seg_cap : 0u);
+    }
     else
     hipLaunchKernelGGL(k_tup_absorb, dim3(grid_for(count, BLOCK)), dim3(BLOCK), 0, c->stream, batch, (const u32*)c->tstore.as<u32>(), rec_off, idx, count,
                        c->ttable.as<TSlot>(), c->tcap - 1, c->list.as<u64>(), key_base,
-                       c->track_order ? 1 : 0, 64u, fail_a, dst,
+                       c->track_order ? 1 : 0, max_probe, fail_a, dst, sbits,
                        fixed_stride, item0);
     HIPC(hipGetLastError());
     c->ttable_clean = false;
@@ -1144,7 +1210,7 @@ int absorb_tuples(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 
       if (c->host_state.ts_words + new_words >= 0x7FFFFFF0ULL) return kamd::fail(-101, "absorb_tuples: more than 2^31 words of distinct tuples");
       if (int rc = c->tstore.ensure((c->host_state.ts_words + new_words + 2) * sizeof(u32), c->host_state.ts_words * sizeof(u32), c->stream)) return rc;
       hipLaunchKernelGGL(k_tup_store, dim3(grid_for(n_new, BLOCK)), dim3(BLOCK), 0, c->stream, batch, c->tstore.as<u32>(), c->ttable.as<TSlot>(),
-                         c->list.as<u64>(), tl_before, n_new, dst);
+                         c->list.as<u64>(), tl_before, n_new, dst, sbits);
       HIPC(hipGetLastError());
       c->host_state.ts_words += new_words;   // (k_tup_store advances the device copy by the same amount)
     }
@@ -1162,6 +1228,13 @@ int absorb_tuples(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 
   HIPC(hipEventElapsedTime(&ms, c->ev_ab0, c->ev_ab1));
   c->last_absorb_ms += ms;
   return 0;
+}
+int absorb_tuples(kamd_ctx* c, const u32* batch, const u64* rec_off, u64 n, u64 batch_words, u64 key_base, u64 n_tuple_bound,
+                  const u64* first_idx, u32 fixed_stride, u64 item0) {
+  if (n == 0) return 0;
+  if (batch_words >= 0x7FFFFFF0ULL) return kamd::fail(-1, "kamd_pseudoalign: the record stream of one batch must stay below 2^31 words (use smaller batches)");
+  if (int rc = absorb_prepare(c, std::min(n, n_tuple_bound), nullptr, true)) return rc;
+  return absorb_rest(c, batch, rec_off, n, batch_words, key_base, first_idx, fixed_stride, item0, nullptr, true);
 }
 
 }  // namespace kamdi

@@ -15,6 +15,7 @@ struct AlignOut {
   u64* explicit_items; // items whose set a positional filter changed (re-run by k_explicit_write)
   u64* explicit_items_big;
   DevState* st;
+  TupleTarget tup;     // k_classify<..., COUNT = true>: the table of distinct tuples, where it counts the short tuple records itself (absorb_prepare)
 };
 
 // Common tail of kernel A: classify one item per lane and emit it (must be called by all 64 lanes of the wavefront).
@@ -277,13 +278,26 @@ __device__ __forceinline__ void wave_lds_fence() {   // the wavefront's LDS writ
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 constexpr int DENSE_CACHE = 2048;
+// the slots a wavefront of k_classify claimed, appended to the list of the distinct tuples' owners (all 64 lanes; n is wavefront-uniform, > 0)
+__device__ __forceinline__ void classify_flush_owners(const u32* won, u32 n, u64* list, DevState* st) {
+  u64 base = 0;
+  if (lane_id() == 0) base = atomicAdd(&st->tl_n, (u64)n);
+  base = shfl_u64(base, 0);
+  for (u32 k = (u32)lane_id(); k < n; k += 64) list[base + k] = (u64)won[k];
+}
 constexpr int CLS_MAX_STRIDE = 2 + V3_LIST_CAP + 4;   // words of a raw record with the positional filters' four
+constexpr int CLS_WON_CAP = 96;   // COUNT: slots a wavefront has claimed and not yet appended to the owners' list (with it the block's LDS still allows four blocks per CU)
 // The slots travel through LDS (end of round 6): a wavefront's 64 slots are one contiguous run of 64 x stride words, read and written back with
 // 16-byte accesses (40 lines per wavefront each way).  Before, every thread read and rewrote its own slot word by word -- up to ten 4-byte
 // accesses each way at a stride of 40 bytes, every one of them 40 line requests per wavefront -- and the kernel ran at the memory system's request
 // rate, not its bandwidth.  The item's set list is built in the slot's own words 2 .. 2 + CAP (the raw classes are in registers by then), so the
 // kernel needs no second LDS array; a slot stride of 10 / 14 words is a 2-way bank conflict.  A wavefront synchronises with itself only.
-template <bool PAIRED, bool FILTER, int CAP>   // CAP: class entries of a raw record (12: kernel A v2, 8: v3)
+// COUNT: a SHORT tuple record (kamd_core.h tuple_tag: the tuple is its own exact tag) is counted into the table of distinct tuples here -- tag load, a
+// compare-and-swap where the slot is empty, the count's atomic -- and its slot is written back as "not a tuple record"; the absorption pass then meets only
+// the long tuples.  No record is compared, so nothing written by this kernel is read by another of its wavefronts; a record that finds no slot within
+// max_probe steps stays a tuple record, and the absorption pass, which meets the same full neighbourhood, puts it on the fail list.  A wavefront keeps the
+// slots it claimed in LDS and appends them to the owners' list CLS_WON_CAP - 64 or more at a time (one same-address atomic per append, not per tile).
+template <bool PAIRED, bool FILTER, int CAP, bool COUNT = false>   // CAP: class entries of a raw record (12: kernel A v2, 8: v3)
 __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict__ slots, int stride, u64 n_items, u64 slot_base,
                                                     u64 rec_base, u64 key_base, u64 item_base, FilterDev fd, AlignOut out) {
   static_assert(2 + CAP + 4 <= CLS_MAX_STRIDE, "slot stride");
@@ -291,12 +305,19 @@ __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict
   __shared__ u32 cache_key[DENSE_CACHE];
   __shared__ u32 cache_cnt[DENSE_CACHE];
   __shared__ u32 cache_min[DENSE_CACHE];  // smallest item index (within this launch) that hit the cached set
-  __shared__ u32 blk_stats[3];
+  __shared__ u32 blk_stats[6];
+  __shared__ u32 won_all[COUNT ? (BLOCK / 64) * CLS_WON_CAP : 1];
   for (int i = threadIdx.x; i < DENSE_CACHE; i += BLOCK) { cache_key[i] = 0xFFFFFFFFu; cache_cnt[i] = 0u; cache_min[i] = 0xFFFFFFFFu; }
-  if (threadIdx.x < 3) blk_stats[threadIdx.x] = 0u;
+  if (threadIdx.x < 6) blk_stats[threadIdx.x] = 0u;
   __syncthreads();
-  u32 s_single = 0, s_multi = 0, s_proc = 0;
+  u32 s_single = 0, s_multi = 0, s_proc = 0, s_counted = 0, s_three_x = 0, s_three_h = 0;
   const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
+  u32* won = won_all + (COUNT ? wv * CLS_WON_CAP : 0);
+  u32 n_won = 0, won_words = 0;   // (wavefront-uniform / this lane's share of the new owners' store words)
+  // the items that stay tuple records, listed for the absorption pass: this wavefront's segment (its tiles x 64 entries at most), no cursor to share
+  const u32 seg = (u32)blockIdx.x * (BLOCK / 64) + (u32)wv;
+  u32* const todo = (COUNT && out.tup.todo) ? out.tup.todo + (u64)seg * out.tup.seg_cap : nullptr;
+  u32 n_todo = 0;
   u32* ws = lds_slots + (size_t)wv * 64 * stride;
   const bool al16 = ((uintptr_t)slots & 15) == 0;   // (a wavefront's run starts at a multiple of 256 x stride bytes)
   for (u64 tile = blockIdx.x; tile * BLOCK < n_items; tile += gridDim.x) {
@@ -312,6 +333,7 @@ __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict
     } else for (u32 k = (u32)lane; k < nwords; k += 64) ws[k] = gsl[k];
     wave_lds_fence();
     const u64 item = wave_item0 + (u64)lane;
+    bool claimed = false, left = false; u32 claimed_slot = 0;
     if (item < n_items) {
     u32* r = ws + lane * stride;
     const u32 h = r[0];
@@ -368,7 +390,23 @@ __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict
       else { atomicAdd(&out.dense_counts[e], 1u); if (out.dense_first) atomicMin(&out.dense_first[e], key_base + item); }
     }
     if (kind == 2) { ++s_multi; r[1] = (u32)ecs.n; }   // (the sets are in place)
+    if (COUNT && kind == 2 && ecs.n <= 3) {
+      const kamd::TupleTag tg = kamd::tuple_tag4((u32)ecs.n, r[2], r[3], ecs.n > 2 ? r[4] : 0u, 0u, out.tup.sbits);
+      if (ecs.n == 3) { if (tg.is_short) ++s_three_x; else ++s_three_h; }
+      if (tg.is_short) {
+        TSlot* const table = out.tup.table;
+        u64 s = tg.start & out.tup.mask;
+        for (u32 probes = 0; probes < out.tup.max_probe; probes++) {
+          u64 old = table[s].tag;   // (plain load first, as in k_tup_absorb: a stale 0 only means the compare-and-swap is taken after all)
+          if (old == 0ULL) old = atomicCAS(&table[s].tag, 0ULL, tg.word);
+          if (old == 0ULL) { claimed = true; claimed_slot = (u32)s; won_words += (u32)ecs.n + 2u; }
+          if (old == 0ULL || old == tg.word) { atomicAdd(&table[s].count, 1ULL); kind = 5; ++s_counted; break; }   // 5: a tuple, counted here
+          s = (s + 1) & out.tup.mask;
+        }
+      }
+    }
     r[0] = kind == 2 ? 1u : 0u;  // record count: 0 = not a tuple record (skipped by the de-duplication)
+    left = kind == 2;
     // (the slot's place is only looked up for the overflow items -- through rec_off until the second pass redirects it to a long record --: every
     // other record of the batch is found by its item number, absorb_tuples' fixed stride)
     if (kind == 3) { out.rec_off[rec_base + item] = slot_base + item * (u64)stride; u64 i = atomicAdd(&out.st->n_overflow, 1ULL); out.overflow_items[i] = item_base + item; }
@@ -381,10 +419,31 @@ __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict
       }
     } else for (u32 k = (u32)lane; k < nwords; k += 64) gsl[k] = ws[k];
     wave_lds_fence();   // (the next tile's loads overwrite the run)
+    if (COUNT) {
+      const u64 bm = __ballot(claimed);
+      if (claimed) won[n_won + (u32)__popcll(bm & ((1ULL << lane) - 1ULL))] = claimed_slot;
+      n_won += (u32)__popcll(bm);
+      if (n_won > (u32)(CLS_WON_CAP - 64)) { wave_lds_fence(); classify_flush_owners(won, n_won, out.tup.list, out.st); n_won = 0; wave_lds_fence(); }
+      if (todo) {
+        const u64 lm = __ballot(left);
+        if (left) todo[n_todo + (u32)__popcll(lm & ((1ULL << lane) - 1ULL))] = (u32)(wave_item0 + (u64)lane);
+        n_todo += (u32)__popcll(lm);
+      }
+    }
+  }
+  if (COUNT) {
+    if (out.tup.todo_cnt && lane == 0) out.tup.todo_cnt[seg] = n_todo;
+    if (n_won) { wave_lds_fence(); classify_flush_owners(won, n_won, out.tup.list, out.st); }
+    const u64 ww = wave_sum64((u64)won_words);
+    if (lane == 0 && ww) atomicAdd(&out.st->bound_words, ww);
   }
   // flush: block-level statistics and the cached single-set counts
   const u64 w_single = wave_sum64((u64)s_single), w_multi = wave_sum64((u64)s_multi), w_proc = wave_sum64((u64)s_proc);
   if (lane_id() == 0) { atomicAdd(&blk_stats[0], (u32)w_single); atomicAdd(&blk_stats[1], (u32)w_multi); atomicAdd(&blk_stats[2], (u32)w_proc); }
+  if (COUNT) {
+    const u64 w_c = wave_sum64((u64)s_counted), w_x = wave_sum64((u64)s_three_x), w_h = wave_sum64((u64)s_three_h);
+    if (lane_id() == 0) { atomicAdd(&blk_stats[3], (u32)w_c); atomicAdd(&blk_stats[4], (u32)w_x); atomicAdd(&blk_stats[5], (u32)w_h); }
+  }
   __syncthreads();
   for (int i = threadIdx.x; i < DENSE_CACHE; i += BLOCK)
     if (cache_cnt[i]) {
@@ -395,6 +454,11 @@ __global__ __launch_bounds__(BLOCK) void k_classify(DevIndex ix, u32* __restrict
     if (blk_stats[0]) atomicAdd(&out.st->st_single, (u64)blk_stats[0]);
     if (blk_stats[1]) atomicAdd(&out.st->st_multi, (u64)blk_stats[1]);
     atomicAdd(&out.st->st_processed, (u64)blk_stats[2]);
+    if (COUNT) {
+      if (blk_stats[3]) atomicAdd(&out.st->cs_counted, (u64)blk_stats[3]);
+      if (blk_stats[4]) atomicAdd(&out.st->cs_three_exact, (u64)blk_stats[4]);
+      if (blk_stats[5]) atomicAdd(&out.st->cs_three_hash, (u64)blk_stats[5]);
+    }
   }
 }
 
@@ -924,9 +988,30 @@ int align_batch(kamd_ctx* c, WorkStream& ws, const u32* d_words, const uint16_t*
   for (int k = 0; k < chunks; k++) {
     const u64 first = (u64)k * per, n = std::min(per, n_items - first);
     if (chunks > 1) HIPC(hipStreamWaitEvent(c->stream, c->al_ev_chunk[k], 0));
-    HIPC(hipEventRecord(c->ev2, c->stream));
+    // k_classify counts the short tuple records itself where that is simple (no positional filter, no mate flags in the ids, no first-occurrence keys):
+    // the table, the owners' list and the fail lists are then sized before it runs, for as many records as the chunk has items
+    const bool count_short = !FILTER && !c->ix.union_mode && !c->track_order && (c->tune.classify_counts_short == 1 || c->tune.classify_counts_short == 3);
     // (persistent blocks: as many as are resident at once -- 38 KB of LDS each, four per CU -- so that none starts when the others are done)
-    const unsigned grid = (unsigned)std::min<u64>(grid_for(n, BLOCK), (u64)std::max(1, c->n_cus) * 4);
+    unsigned grid = (unsigned)std::min<u64>(grid_for(n, BLOCK), (u64)std::max(1, c->n_cus) * 4);
+    if (c->tune.classify_max_blocks > 0) grid = std::min(grid, (unsigned)c->tune.classify_max_blocks);   // (test hook: several tiles per block on a small batch)
+    if (count_short) {
+      if (n * (u64)stride >= 0x7FFFFFF0ULL) return kamd::fail(-1, "kamd_pseudoalign: the record stream of one batch must stay below 2^31 words (use smaller batches)");
+      if (int rc = absorb_prepare(c, n, &out.tup, false)) return rc;
+      if (c->tune.classify_counts_short == 1) {
+        // what k_classify leaves to the absorption pass, listed: a segment per wavefront of the launch, sized for the tiles a block can take
+        const u32 n_segs = grid * (BLOCK / 64), seg_cap = (u32)((grid_for(n, BLOCK) + grid - 1) / grid) * 64u;
+        if (int rc = c->todo.ensure((u64)n_segs * seg_cap * sizeof(u32), 0, c->stream)) return rc;
+        if (int rc = c->todo_cnt.ensure((u64)n_segs * sizeof(u32), 0, c->stream)) return rc;
+        out.tup.todo = c->todo.as<u32>(); out.tup.todo_cnt = c->todo_cnt.as<u32>(); out.tup.n_segs = n_segs; out.tup.seg_cap = seg_cap;
+      }
+    }
+    HIPC(hipEventRecord(c->ev2, c->stream));
+    if constexpr (!FILTER) {
+      if (count_short)
+        hipLaunchKernelGGL((k_classify<PAIRED, false, V3_LIST_CAP, true>), dim3(grid), dim3(BLOCK), 0, c->stream, c->ix, slots + first * (u64)stride, stride, n,
+                           first * (u64)stride, first, key_base + first, first, fd, out);
+    }
+    if (!count_short)
     hipLaunchKernelGGL((k_classify<PAIRED, FILTER, V3_LIST_CAP>), dim3(grid), dim3(BLOCK), 0, c->stream, c->ix, slots + first * (u64)stride, stride, n,
                        first * (u64)stride, first, key_base + first, first, fd, out);
     HIPC(hipGetLastError());
@@ -941,6 +1026,10 @@ int align_batch(kamd_ctx* c, WorkStream& ws, const u32* d_words, const uint16_t*
       if (sr < 0) return sr;
     }
     // the chunk's tuple records join the distinct tuples of the run (overflow items have no tuple record yet: see kamd_pseudoalign)
+    // (where k_classify has counted the short ones the pass is already prepared, and the owners k_classify made go into the store with its own)
+    if (count_short) {
+      if (int rc = absorb_rest(c, c->stream_buf.as<u32>(), c->rec_off.as<u64>() + first, n, c->host_state.stream_words, key_base + first, nullptr, (u32)stride, first, &out.tup, false)) return rc;
+    } else
     if (int rc = absorb_tuples(c, c->stream_buf.as<u32>(), c->rec_off.as<u64>() + first, n, c->host_state.stream_words, key_base + first,
                                c->host_state.st_multi - c->multi_before, nullptr, (u32)stride, first)) return rc;
     c->multi_before = c->host_state.st_multi;
@@ -1209,6 +1298,7 @@ extern "C" int kamd_align_stats_get(kamd_ctx* c, kamd_align_stats* s) {
   s->n_raw_words = sa.raw_words;
   s->n_text_hits = sa.text_hits;
   s->n_wave_iters = sa.wave_iters; s->n_lane_iters = sa.lane_iters;
+  s->n_classify_counted = c->host_state.cs_counted; s->n_three_exact = c->host_state.cs_three_exact; s->n_three_hashed = c->host_state.cs_three_hash;
   return 0;
 }
 

@@ -125,7 +125,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 14
+#define KAMD_ABI_VERSION 15
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -172,7 +172,7 @@ int kamd_index_check_opts(const kamd_index*, const kamd_quant_opts*);
  * 0 in a field = keep the current value; on/off fields use 1 = on, 2 = off. */
 typedef struct {
   int32_t text_verify;         /* kernel A: jump / middle / back-off windows are compared with the unitig text first (default on) */
-  int32_t items_per_wave;      /* items per wavefront chunk of kernel A (default 1024, >= 64) */
+  int32_t items_per_wave;      /* kernel A in its fixed-chunk form (match_continuous off): items per wavefront chunk (default 1024, >= 64) */
   int32_t refill_min;          /* free lanes that trigger a refill (default 8, 1..64) */
   int32_t lds_pad;             /* diagnostic: unused LDS bytes added to every block of kernel A (lowers the occupancy); -1 = none */
   int32_t em_form;             /* EM: 1 = streamed two-launch form, 2 = CSR three-launch form (also what degenerate matrices -- no row with two
@@ -231,6 +231,13 @@ typedef struct {
   int32_t tup_max_probe;       /* test hook: slots a tuple record tries before it goes to the fail list and the table grows (1..64; default 64) */
   int32_t classify_max_blocks; /* test hook: at most this many persistent blocks of k_classify (-1 = as many as are resident at once, the default), so that a
                                   small batch gives a block several tiles */
+  int32_t match_continuous;    /* kernel A: 1 (default) = persistent blocks, as many as are resident at once, whose wavefronts take their items in grants of
+                                  match_grant positions from one cursor per launch and refill their lanes across grant boundaries; 2 = the fixed-chunk form:
+                                  a wavefront per chunk of items_per_wave items, as many blocks as that takes (for comparisons in one build) */
+  int32_t match_grant;         /* continuous feed: positions per grant (default 256, >= 64, any value; the second pass over the overflow items takes fewer where it
+                                  has few items) */
+  int32_t match_max_blocks;    /* test hook, continuous feed: at most this many blocks of kernel A, so that a few wavefronts take every grant of a small batch;
+                                  reported as 0 = no cap (the default); since 0 in a field keeps its value, a negative value takes the cap away */
 } kamd_tuning;
 int kamd_ctx_tune(kamd_ctx*, const kamd_tuning*);
 int kamd_ctx_get_tuning(const kamd_ctx*, kamd_tuning* out);
@@ -308,7 +315,8 @@ int kamd_fastq_unit_pack(kamd_ctx*, const char* const* d_text, const uint64_t* n
  * n_items = pairs (paired) or reads (single).  Accumulates into the context's EC state; call kamd_ec_finalize after
  * the last batch.  The EC state is bounded by the number of DISTINCT classes, like MinCollector's (src/MinCollector.cpp:251-269): a
  * dense count vector over the index's transcript sets plus a table of the distinct tuples of set ids seen so far; the per-item
- * records of a batch are recycled when the call returns.
+ * records of a batch are recycled when the call returns.  A batch holds fewer than 3 x 2^30 items (-1 otherwise: kernel A keeps an item's
+ * position in the batch in 32 bits); a larger input is given in several calls.
  * An index with shades (kamd_index_view::n_shades != 0): the EC state is the same -- dense counts and tuples of set ids --, and kamd_ec_finalize
  * resolves a tuple as the intersection of its sets' cores with every shade of any of its sets united back in whose colour is in it; match() runs
  * with partial = false and a strand option filters per hit; -5 for fld != 0 without single_overhang (kamd_index_check_opts). */

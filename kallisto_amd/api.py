@@ -60,11 +60,11 @@ class Tuning(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("text_verify", "items_per_wave", "refill_min", "lds_pad", "em_form", "em_entries_per_lane", "em_windowed", "em_graph", "em_row_lanes",
                                          "em_fin_blocks", "em_local_block", "em_group_div", "em_split_len", "dedup_form", "align_chunks", "em_small_nnz", "em_reg_slices",
                                          "em_hybrid", "overflow_second_pass", "em_giant_nnz", "em_blocked", "fld_list_cap", "fld_first_chunk", "classify_counts_short",
-                                         "short_id_bits", "tup_max_probe", "classify_max_blocks")]
+                                         "short_id_bits", "tup_max_probe", "classify_max_blocks", "match_continuous", "match_grant", "match_max_blocks")]
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 14   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 15   # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):

@@ -406,6 +406,51 @@ KAMD_HD uint32_t tuple_of_tag(uint64_t word, uint32_t short_id_bits, uint32_t* i
   return 2;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// kernel A's item feed: the positions [0, n) of a launch, handed to its wavefronts in grants of `grant` positions from ONE cursor (a wavefront's
+// atomicAdd(cursor, grant) returns where its grant begins).  A wavefront holds the grant it is handing to its lanes and, asked for before that one runs
+// out, the grant behind it; lanes are refilled across the boundary.  The fixed-chunk form is the same feed with one grant given at the start and
+// no request ever made.  Everything here is wavefront-uniform; the kernel and the CPU emulation (tests/emu_matchfeed) call the same functions.
+// ---------------------------------------------------------------------------------------------------------------
+struct ItemFeed {
+  uint32_t lo, hi;     // the current grant: positions [lo, hi) that no lane has taken yet
+  uint32_t nlo, nhi;   // the grant behind it (none: nlo == nhi)
+  bool dry;            // no further request: a grant reached n (or the wavefront owns a fixed chunk)
+};
+// Positions are 32-bit (wavefront-uniform registers are what kernel A is short of): a launch has fewer than FEED_MAX_ITEMS positions and a grant at
+// most FEED_MAX_GRANT, so that the cursor stays below 2^32 however many wavefronts ask once more than they need.
+static const uint32_t FEED_AHEAD = 64;   // the next grant is asked for when fewer positions than this are left of the current one
+static const uint32_t FEED_MAX_GRANT = 1u << 16;
+static const uint64_t FEED_MAX_ITEMS = 3ULL << 30;
+KAMD_HD ItemFeed feed_fixed(uint32_t lo, uint32_t hi) { ItemFeed f; f.lo = lo; f.hi = hi < lo ? lo : hi; f.nlo = f.nhi = 0; f.dry = true; return f; }
+KAMD_HD ItemFeed feed_open() { ItemFeed f; f.lo = f.hi = f.nlo = f.nhi = 0; f.dry = false; return f; }
+// positions the wavefront can hand out now
+KAMD_HD uint32_t feed_avail(const ItemFeed& f) { return (f.hi - f.lo) + (f.nhi - f.nlo); }
+KAMD_HD bool feed_wants_grant(const ItemFeed& f) { return !f.dry && f.nlo == f.nhi && f.hi - f.lo < FEED_AHEAD; }
+KAMD_HD bool feed_finished(const ItemFeed& f) { return f.dry && f.lo == f.hi && f.nlo == f.nhi; }
+// the answer to a request: `start` is what the cursor held before this wavefront added `grant` to it
+KAMD_HD void feed_grant(ItemFeed& f, uint32_t start, uint32_t grant, uint32_t n) {
+  if (start >= n) { f.dry = true; return; }
+  uint32_t end = start + grant;
+  if (end >= n) { end = n; f.dry = true; }   // (the cursor has passed n: whatever is asked for after this lies beyond it)
+  if (f.lo == f.hi) { f.lo = start; f.hi = end; }
+  else { f.nlo = start; f.nhi = end; }
+}
+// the position of the r-th (0, 1, ..) of the lanes that take an item in this iteration; false: nothing left for it now
+KAMD_HD bool feed_pos(const ItemFeed& f, uint32_t r, uint32_t* pos) {
+  const uint32_t c = f.hi - f.lo;
+  if (r < c) { *pos = f.lo + r; return true; }
+  if (r - c < f.nhi - f.nlo) { *pos = f.nlo + (r - c); return true; }
+  return false;
+}
+// `want` lanes asked: the first feed_avail() of them were served
+KAMD_HD void feed_advance(ItemFeed& f, uint32_t want) {
+  const uint32_t c = f.hi - f.lo;
+  if (want < c) { f.lo += want; return; }
+  const uint32_t c2 = f.nhi - f.nlo, k = want - c < c2 ? want - c : c2;
+  f.lo = f.nlo + k; f.hi = f.nhi; f.nlo = f.nhi = 0;   // (no grant behind it: nlo == nhi == 0, the current one is empty)
+}
+
 struct MateInfo {
   int n_hits;        // v.size()
   int n_nonempty;    // != 0 when some hit carries a non-empty transcript set
@@ -577,7 +622,7 @@ KAMD_HD void ueclist_add(UecList& l, uint32_t uec, int mate) {
   l.e[l.n * l.stride] = uec | flag;
   ++l.n;
 }
-struct MateFirst { int n_hits; uint64_t slot; int pos; bool strand; };
+struct MateFirst { int n_hits; uint32_t slot; int pos; bool strand; };   // (slot: its low word, which is what kernel A's raw record keeps of it)
 
 // the table the pending probe of a phase goes to
 KAMD_HD Table phase_table(const Table& t, int phase) { return phase == PH_DLIST ? Table{t.dslots, t.n_dbuckets} : t; }

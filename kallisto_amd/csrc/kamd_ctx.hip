@@ -11,6 +11,7 @@ void tuning_defaults(kamd_tuning* t) {
   t->em_hybrid = 1; t->overflow_second_pass = 1; t->em_giant_nnz = -1; t->em_blocked = 1;
   t->fld_list_cap = 64; t->fld_first_chunk = 1048576;
   t->classify_counts_short = 1; t->short_id_bits = (int32_t)kamd::SHORT_ID_BITS_MAX; t->tup_max_probe = 64; t->classify_max_blocks = -1;
+  t->match_continuous = 1; t->match_grant = 256; t->match_max_blocks = 0;
 }
 // 0 = keep; values outside a field's range are ignored
 void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
@@ -42,6 +43,9 @@ void tuning_merge(kamd_tuning* t, const kamd_tuning& n) {
   if (n.short_id_bits >= 4 && n.short_id_bits <= (int32_t)kamd::SHORT_ID_BITS_MAX) t->short_id_bits = n.short_id_bits;
   if (n.tup_max_probe >= 1 && n.tup_max_probe <= 64) t->tup_max_probe = n.tup_max_probe;
   if (n.classify_max_blocks != 0) t->classify_max_blocks = n.classify_max_blocks < 0 ? -1 : n.classify_max_blocks;
+  if (n.match_continuous == 1 || n.match_continuous == 2) t->match_continuous = n.match_continuous;
+  if (n.match_grant >= 64) t->match_grant = std::min(n.match_grant, (int32_t)kamd::FEED_MAX_GRANT);
+  if (n.match_max_blocks != 0) t->match_max_blocks = n.match_max_blocks < 0 ? 0 : n.match_max_blocks;
 }
 // experiments: the same knobs from ONE environment variable, read once when a context is created --
 //   KAMD_TUNE="em_form=streamed,em_graph=0,items_per_wave=512"   (field names of kamd_tuning; on/off fields take 1 / 0; em_form also by name)
@@ -61,7 +65,8 @@ void tuning_from_env(kamd_tuning* t) {
     {"overflow_second_pass", &kamd_tuning::overflow_second_pass, false}, {"em_giant_nnz", &kamd_tuning::em_giant_nnz, false}, {"em_blocked", &kamd_tuning::em_blocked, true},
     {"fld_list_cap", &kamd_tuning::fld_list_cap, false}, {"fld_first_chunk", &kamd_tuning::fld_first_chunk, false},
     {"classify_counts_short", &kamd_tuning::classify_counts_short, false}, {"short_id_bits", &kamd_tuning::short_id_bits, false},
-    {"tup_max_probe", &kamd_tuning::tup_max_probe, false}, {"classify_max_blocks", &kamd_tuning::classify_max_blocks, false}};
+    {"tup_max_probe", &kamd_tuning::tup_max_probe, false}, {"classify_max_blocks", &kamd_tuning::classify_max_blocks, false},
+    {"match_continuous", &kamd_tuning::match_continuous, true}, {"match_grant", &kamd_tuning::match_grant, false}, {"match_max_blocks", &kamd_tuning::match_max_blocks, false}};
   std::string all(e);
   for (size_t pos = 0; pos < all.size();) {
     size_t end = all.find(',', pos);
@@ -204,7 +209,7 @@ extern "C" void kamd_ctx_destroy(kamd_ctx* c) {
   if (c->sell_cache) sell_cache_free(c->sell_cache);
   for (void* p : c->index_allocs) (void)hipFree(p);
   for (DBuf* b : {&c->dense, &c->stream_buf, &c->rec_off, &c->overflow_items, &c->overflow_scratch, &c->state, &c->rec_slot,
-                  &c->retry, &c->ttable, &c->tstore, &c->todo, &c->todo_cnt, &c->stats_a, &c->list, &c->cand, &c->cand_off, &c->cand_slot, &c->ctable, &c->tup_bound, &c->tup_off, &c->tup_big, &c->raw2, &c->overflow_left, &c->stats_b, &c->clist, &c->sizes, &c->explicit_items,
+                  &c->retry, &c->ttable, &c->tstore, &c->todo, &c->todo_cnt, &c->stats_a, &c->list, &c->cand, &c->cand_off, &c->cand_slot, &c->ctable, &c->tup_bound, &c->tup_off, &c->tup_big, &c->raw2, &c->overflow_left, &c->stats_b, &c->match_cursor, &c->clist, &c->sizes, &c->explicit_items,
                   &c->explicit_items_big, &c->exp_stream, &c->exp_off, &c->exp_scratch, &c->bs_cp, &c->bs_samp, &c->raw, &c->dense_first, &c->exp_key, &c->cand_key, &c->ec_first, &c->pm_a, &c->pm_b, &c->pm_rank, &c->eml_tmp, &c->ems_tmp, &c->ems_plan, &c->ems_maps, &c->fld_tl, &c->fld_card, &c->fld_scratch, &c->fld_items, &c->fld_cand,
                   &c->block_sums, &c->ec_off, &c->ec_ids, &c->ec_counts, &c->em_alpha, &c->em_next, &c->em_eff,
                   &c->em_state, &c->em_cn, &c->em_colcnt, &c->em_coloff, &c->em_colrow,

@@ -319,6 +319,9 @@ struct kamd_ctx {
   float last_align_ms = 0.f, last_em_ms = 0.f, last_classify_ms = 0.f;
   hipEvent_t ev2 = nullptr, ev3 = nullptr, ev_fin0 = nullptr, ev_fin1 = nullptr;
   DBuf stats_a;                  // DevStatsA: kernel A's counters
+  DBuf match_cursor;             // kernel A's continuous feed: one position cursor per launch of a batch: its chunks and the second pass (kamd_match.hip MATCH_CURSORS)
+  struct MatchOcc { const void* kernel; size_t lds_bytes; int per_cu; };
+  std::vector<MatchOcc> match_occ;   // ... and the resident blocks per CU of the instantiations launched so far, by dynamic LDS size (match_grid)
   hipStream_t al_stream = nullptr; hipEvent_t al_ev_in = nullptr, al_ev_out = nullptr; std::vector<hipEvent_t> al_ev_chunk;   // kamd_pseudoalign's side stream (WorkStream)
   float last_finalize_ms = 0.f; u64 last_fin_records = 0, last_fin_stream_words = 0, last_fin_cand_words = 0;
   hipStream_t em_stream = nullptr;

@@ -79,8 +79,8 @@ __device__ __forceinline__ void emit_item(const DevIndex& ix, const FilterDev& f
 // ------------------------------------------------------------------------------------------------------------------
 // Kernel A: per-lane match() state machines (kamd_core.h MatchState).
 //   k_match_v3   every lane owns a resumable match(); every iteration all busy lanes issue one memory access together, and a
-//                lane that finishes its item takes the next one of the wavefront's chunk, its packed reads being fetched while
-//                the others probe.  Reads live in a lane-transposed LDS layout (word j of lane i at [j*64+i]: conflict-free).
+//                lane that finishes its item takes the next one of the wavefront's feed (grants from a launch-wide cursor, or a
+//                fixed chunk), its packed reads being fetched while the others probe.  Reads live in a lane-transposed LDS layout (word j of lane i at [j*64+i]: conflict-free).
 //                Output: one raw record per item {header, distinct (unitig,set) classes}.
 //   k_classify   one thread per item: classes -> sorted distinct transcript-set ids, then the common emit_item tail.
 // (The two earlier versions -- block-staged reads with a straight-line match per lane, 42 ms; one table probe per iteration with
@@ -97,20 +97,36 @@ constexpr u32 RAW_OVERFLOW = 1u << 8, RAW_HIT0 = 1u << 9, RAW_HIT1 = 1u << 10;
 //     config #3 a quarter of all probes (every successful jump) never touch the 2.4 GB table;
 //   * 24 words of LDS per lane instead of 38 (sequence words of both mates + 8 classes; the non-ACGT plane stays in global
 //     memory and is only read for items whose record carries the has-N flag): 24 wavefronts per CU instead of 16;
-//   * items handed out from a wavefront-uniform cursor (ballot + prefix count, no LDS atomic), class lists thread-transposed
+//   * items handed to the lanes from wavefront-uniform registers (ballot + prefix count, no LDS atomic), class lists thread-transposed
 //     in LDS (conflict-free), and the 32-bit k-mer hash.
 // More than V3_LIST_CAP distinct classes (0.5 % of config #3's pairs): the item goes to the overflow kernel, as before.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int V3_LIST_CAP = 8;
 constexpr int V3_LIST_CAP_LONG = 192;   // the second pass over the items whose list overflowed (k_match_v3<..., V3_LIST_CAP_LONG, true> on an item list)
 // LCAP: class entries per item (in LDS; APPEND: in the item's raw record in global memory, appended, never scanned -- kamd_core.h UecList).
-// item_idx != null: the launch works on the items item_idx[0 .. n_items) of the batch (their raw records go to slots 0 .. n_items of `raw`):
+// APPEND (item_idx is then required): the launch works on the items item_idx[0 .. n_items) of the batch (their raw records go to slots 0 .. n_items of `raw`):
 // the second pass over the items whose list overflowed in the first -- a pair inside a repeat family or a poly-A stretch has dozens of
 // distinct classes --, with the same data-flow matcher at the same occupancy instead of 64 divergent straight-line ones per wavefront.
+// Wavefronts per SIMD of each form, held as the register allocator's floor: what the forms had with the fixed chunks alone (tools/kernel_resources.py
+// on that build).  The feed's cursor, grant and look-ahead are a handful of registers more, and most forms sat exactly on a boundary of the register
+// file (72 / 80 / 96 VGPRs for 7 / 6 / 5 wavefronts): left to itself the allocator gave a fifth of them one wavefront less.  Index: APPEND, PAIRED,
+// FILTER, DL, TEXT, LAYOUT == compact, most significant first.
+// A floor turns a register too many into a spill, not into a lost wavefront, and no test sees either.  After a change to the loop or a new compiler,
+// from kallisto_amd/csrc:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Rpass-analysis=kernel-resource-usage -c kamd_match.hip -o /dev/null 2> match.remarks
+//   ../../tools/kernel_resources.py table match.remarks > match.md
+// Every k_match_v3 row of match.md must show 0 under scratch and under VGPR spills and at least this table's figure under occupancy
+// (`tools/kernel_resources.py diff` against the table of the commit before shows what moved); a form that spills gets its entry lowered.
+constexpr unsigned char V3_WAVES_PER_SIMD[64] = {7, 7, 7, 7, 7, 7, 7, 6,  7, 7, 6, 6, 7, 7, 6, 5,  7, 7, 6, 6, 7, 7, 6, 6,  7, 7, 5, 5, 6, 6, 5, 5,
+                                                 7, 7, 7, 7, 7, 7, 7, 6,  7, 7, 6, 6, 7, 7, 6, 5,  7, 7, 6, 6, 7, 7, 6, 5,  6, 6, 5, 5, 6, 5, 5, 5};
+constexpr int v3_waves(bool paired, bool filter, bool dl, bool text, int layout, bool append) {
+  return V3_WAVES_PER_SIMD[(append ? 32 : 0) + (paired ? 16 : 0) + (filter ? 8 : 0) + (dl ? 4 : 0) + (text ? 2 : 0) + (layout == kamd::LAYOUT_COMPACT ? 1 : 0)];
+}
 template <bool PAIRED, bool FILTER, bool DL, bool TEXT, int LAYOUT, int LCAP = V3_LIST_CAP, bool APPEND = false>
-__global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __restrict__ words, const uint16_t* __restrict__ lens,
+__global__ __launch_bounds__(BLOCK, v3_waves(PAIRED, FILTER, DL, TEXT, LAYOUT, APPEND)) void k_match_v3(DevIndex ix, const u32* __restrict__ words, const uint16_t* __restrict__ lens,
                                                     u64 n_items, int seq_words, int rec_words, int items_per_wave, int refill_min,
-                                                    u32* raw, int raw_stride, DevStatsA* st, const u64* __restrict__ item_idx = nullptr) {
+                                                    u32* raw, int raw_stride, DevStatsA* st, u32* feed_cursor, u32 grant,
+                                                    const u64* __restrict__ item_idx = nullptr) {
   extern __shared__ __attribute__((aligned(16))) u32 lds[];
   constexpr int WAVES = BLOCK / 64;
   constexpr int NM = PAIRED ? 2 : 1;
@@ -120,10 +136,19 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
   u32* wave_words = lds + (size_t)wv * 64 * lane_words;       // the wavefront's items, lane-transposed
   u32* my_words = wave_words + lane;                          // word j at my_words[j * 64]
   u32* my_list = APPEND ? nullptr : lds + (size_t)WAVES * 64 * lane_words + threadIdx.x;   // entry j at my_list[j * BLOCK]
-  const u64 wave_global = (u64)blockIdx.x * WAVES + wv;
-  const u64 chunk0 = wave_global * (u64)items_per_wave;
-  const u32 chunk_n = chunk0 < n_items ? (u32)min((u64)items_per_wave, n_items - chunk0) : 0u;
-  u32 cursor = 0;                                             // next item of the chunk (wavefront-uniform)
+  // The wavefront's share of the launch's positions [0, n_items) (kamd_core.h ItemFeed, wavefront-uniform): grants of `grant` positions from the
+  // launch-wide cursor, or -- no cursor -- the fixed chunk [w * items_per_wave, + items_per_wave) of wavefront w of the grid, which is the same feed
+  // with its one grant made here.  Position p is slot p of `raw` and item p (item_idx[p]) of the batch.
+  kamd::ItemFeed items;
+  if (feed_cursor) {
+    items = kamd::feed_open();
+    u32 start = 0;
+    if (lane == 0) start = atomicAdd(feed_cursor, grant);
+    kamd::feed_grant(items, (u32)__builtin_amdgcn_readfirstlane((int)start), grant, (u32)n_items);
+  } else {
+    const u64 chunk0 = ((u64)blockIdx.x * WAVES + wv) * (u64)items_per_wave;
+    items = kamd::feed_fixed((u32)min(chunk0, n_items), (u32)min(chunk0 + (u64)items_per_wave, n_items));
+  }
   const kamd::Table t = make_table(ix, !PAIRED);
   const int k = ix.k;
 
@@ -132,30 +157,34 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
   kamd::UecList ul{my_list, LCAP, 0, false, APPEND ? 1 : BLOCK};
   ul.append = APPEND;
   kamd::MateFirst mf0{0, 0, -1, false}, mf1{0, 0, -1, false};
-  u64 my_item = 0;        // the lane's item in the batch (chunk0 + my_idx, or item_idx[chunk0 + my_idx])
-  int mate = 0, len0 = 0, len1 = 0;
+  u32 listed_item = 0;    // APPEND: the lane's item in the batch, item_idx[my_pos] (the first pass takes the items in order: my_pos itself)
+  int mate = 0;
+  u32 lens01 = 0;         // the two mates' lengths, 16 bits each (one register)
   bool n0 = false, n1 = false;   // has-N flags of the two mates
-  u32 my_idx = 0;
+  u32 my_pos = 0;         // ... and its position in the launch (fewer than kamd::FEED_MAX_ITEMS)
   bool have = false;      // the lane owns an item whose raw record is not written yet
   bool busy = false;      // ... and its state machine still wants probes
-  bool exhausted = false;
-  u32 probes = 0, breads = 0, raw_words = 0, text_hits = 0;
+  u32 raw_words = 0;
+  u32 probes = 0, breads = 0, text_hits = 0;   // counted for the wavefront (a ballot behind the probe: per-lane counters are registers this kernel has not got)
   u32 wave_iters = 0, lane_iters = 0;   // loop trips of this wavefront / lanes that probed in them (lane utilisation of the kernel)
 
   for (;;) {
-    // 1. lanes without an item take the next ones of the chunk; their sequence words come by LDS-DMA loads, in flight during
-    // the probe below.  Refills are batched (at least refill_min free lanes, or nothing left to probe).
+    // 0. fewer than a wavefront's worth of positions left and no grant behind them: ONE lane asks the cursor for the next grant.  The answer is
+    // looked at behind the probes of this iteration (3b), which were issued after it and are waited for anyway; nothing waits for another wavefront.
+    const bool ask = kamd::feed_wants_grant(items);
+    u32 granted = 0;
+    if (ask && lane == 0) granted = atomicAdd(feed_cursor, grant);
+    // 1. lanes without an item take the next positions of the feed, across the boundary of two grants; their sequence words come by LDS-DMA
+    // loads, in flight during the probe below.  Refills are batched (at least refill_min free lanes, or nothing left to probe).
     bool loading = false;
-    const u64 idle_mask = __ballot(!have && !exhausted);
-    const bool do_refill = idle_mask != 0ULL && (__popcll(idle_mask) >= refill_min || __ballot(have) == 0ULL);
+    const u64 idle_mask = __ballot(!have);
+    const bool do_refill = idle_mask != 0ULL && kamd::feed_avail(items) != 0u && (__popcll(idle_mask) >= refill_min || __ballot(have) == 0ULL);
     if (do_refill) {
-      if (!have && !exhausted) {
-        my_idx = cursor + (u32)__popcll(idle_mask & ((1ULL << lane) - 1ULL));
-        if (my_idx >= chunk_n) exhausted = true;
-        else {
+      if (!have) {
+        if (kamd::feed_pos(items, (u32)__popcll(idle_mask & ((1ULL << lane) - 1ULL)), &my_pos)) {
           loading = true;
-          const u64 item = item_idx ? item_idx[chunk0 + my_idx] : chunk0 + my_idx;
-          my_item = item;
+          const u64 item = APPEND ? item_idx[my_pos] : (u64)my_pos;
+          if (APPEND) listed_item = (u32)item;
           const u32* src = words + item * item_words;
 #pragma unroll 4
           for (int j = 0; j < seq_words; j++)
@@ -167,18 +196,22 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
               __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + rec_words + j),
                                                (__attribute__((address_space(3))) void*)(wave_words + (size_t)(seq_words + j) * 64), 4, 0, 0);
           }
-          len0 = PAIRED ? (int)lens[2 * item] : (int)lens[item];
-          len1 = PAIRED ? (int)lens[2 * item + 1] : 0;
+          lens01 = PAIRED ? (u32)lens[2 * item] | ((u32)lens[2 * item + 1] << 16) : (u32)lens[item];
         }
       }
-      cursor += (u32)__popcll(idle_mask);
+      kamd::feed_advance(items, (u32)__popcll(idle_mask));
     }
-    if (__ballot(have || loading) == 0ULL) break;
+    if (__ballot(have || loading) == 0ULL && kamd::feed_finished(items)) break;   // (not finished: the grant asked for above is on its way)
+    // (a wavefront that holds no item and waits for a grant -- at the start or the end of a launch, when a refill wanted more than was left -- still
+    // counts a trip without a busy lane: lane utilisation is reported that much lower, the truth about those iterations)
     ++wave_iters; lane_iters += (u32)__popcll(__ballot(have && busy));
     // 2. every busy lane: ONE memory request -- the unitig text where the window's place on the unitig is known, else a bucket
     // of the table -- all of them issued before any is waited for; a text mismatch or a bucket whose continue flag sends the
     // key to the next bucket costs the lane another iteration, never the wavefront a second round trip
+    bool did_read = false, did_probe = false, did_hit = false;
+    const int len0 = (int)(lens01 & 0xFFFFu), len1 = (int)(lens01 >> 16);
     if (have && busy) {
+      const u64 my_item = APPEND ? (u64)listed_item : (u64)my_pos;
       const u32* base = my_words + (size_t)(mate ? seq_words : 0) * 64;
       const u32* mplane = words + my_item * (u64)item_words + (size_t)(mate ? rec_words : 0) + seq_words;
       kamd::ReadView rv{base, mplane, mate ? len1 : len0, 64, 1, mate ? n1 : n0};
@@ -194,18 +227,19 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
       kamd::TextWords tw{0u, 0u, 0u};
       kamd::BucketLine bl{0, 0, 0, 0, 0, 0, 0, 0};
       if (use_text) tw = kamd::load_text(ix.utext, tpos);
-      else { bl = kamd::load_bucket(pt.slots, bucket); ++breads; }
+      else { bl = kamd::load_bucket(pt.slots, bucket); did_read = true; }
       kamd::Probe p; p.found = false; p.strand = false; p.uec = kamd::NO_UEC; p.dist = 0; p.slot = 0; p.gpos = 0;
       bool feed = true;
       if (use_text) {
-        if (kamd::text_canon_of(tw, tpos, k) == canon) { p.found = true; p.strand = ms.um_strand; p.uec = ms.um_uec; ++text_hits; }   // (only uec is looked at in these phases)
+        if (kamd::text_canon_of(tw, tpos, k) == canon) { p.found = true; p.strand = ms.um_strand; p.uec = ms.um_uec; did_hit = true; }   // (only uec is looked at in these phases)
         else { ms.text_tried = true; feed = false; }
       } else if (compact) {
         if (kamd::match_bucket_compact(bl, pt, kamd::compact_tag(pt, canon, khash, ms.disp), fc, bucket, p) == kamd::BUCKET_CONTINUE &&
             ms.disp < kamd::compact_max_disp(pt)) { ++ms.disp; feed = false; }
       } else if (kamd::match_bucket(bl, canon, fc, bucket, p) == kamd::BUCKET_CONTINUE) { ++ms.disp; feed = false; }
       if (feed) {
-        if (!DL || ms.phase != kamd::PH_DLIST) ++probes;   // dbg.find calls of match(); the D-list scan is counted as bucket reads only
+        did_probe = !DL || ms.phase != kamd::PH_DLIST;   // dbg.find calls of match(); the D-list scan is counted as bucket reads only
+        if (APPEND) ul.e = raw + (u64)my_pos * (u64)raw_stride + 1;   // the item's classes go straight into its raw record (worked out here: not a register pair kept over the loop)
         kamd::match_feed<DL>(ms, rv, k, p, ul, mate, mate ? mf1 : mf0, t);
         if (ms.phase == kamd::PH_DONE && PAIRED && mate == 0) {
           mate = 1;
@@ -216,16 +250,17 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
         busy = ms.phase != kamd::PH_DONE;
       }
     }
+    breads += (u32)__popcll(__ballot(did_read)); probes += (u32)__popcll(__ballot(did_probe));
+    if (TEXT) text_hits += (u32)__popcll(__ballot(did_hit));
     // 3. lanes that fetched an item: its words are in LDS once the DMA loads have landed; start mate 1
     if (loading) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       ul.n = 0; ul.overflow = false; ul.last = kamd::NO_UEC; ul.last_flags = 0;
-      if (APPEND) ul.e = raw + (chunk0 + my_idx) * (u64)raw_stride + 1;   // the item's classes go straight into its raw record
       mf0 = kamd::MateFirst{0, 0, -1, false}; mf1 = kamd::MateFirst{0, 0, -1, false};
       mate = 0;
       n0 = (my_words[(size_t)(seq_words - 1) * 64] & kamd::REC_FLAG_HAS_N) != 0;
       n1 = PAIRED ? (my_words[(size_t)(2 * seq_words - 1) * 64] & kamd::REC_FLAG_HAS_N) != 0 : false;
-      const u32* mplane = words + my_item * (u64)item_words + seq_words;
+      const u32* mplane = words + (APPEND ? (u64)listed_item : (u64)my_pos) * (u64)item_words + seq_words;
       kamd::ReadView r0{my_words, mplane, len0, 64, 1, n0};
       kamd::match_init(ms, r0, k);
       if (ms.phase == kamd::PH_DONE && PAIRED) {
@@ -237,9 +272,11 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
       have = true;
       busy = ms.phase != kamd::PH_DONE;
     }
+    // 3b. the grant asked for in 0.
+    if (ask) kamd::feed_grant(items, (u32)__builtin_amdgcn_readfirstlane((int)granted), grant, (u32)n_items);
     // 4. finished items: write the raw record (plain stores, nothing waits for them) and free the lane
     if (have && !busy) {
-      u32* o = raw + (chunk0 + my_idx) * (u64)raw_stride;
+      u32* o = raw + (u64)my_pos * (u64)raw_stride;
       if constexpr (!APPEND) {
         // (words 0 .. n of the slot in 8-byte stores -- a slot starts at a multiple of 40 bytes --: on average two requests per item instead of three
         // and a half, in a kernel that lives on the memory system's request rate; the word behind the last class is whatever the list held)
@@ -259,10 +296,10 @@ __global__ __launch_bounds__(BLOCK) void k_match_v3(DevIndex ix, const u32* __re
       have = false;
     }
   }
-  const u64 s_probes = wave_sum64((u64)probes), s_reads = wave_sum64((u64)breads), s_raw = wave_sum64((u64)raw_words), s_text = wave_sum64((u64)text_hits);
+  const u64 s_raw = wave_sum64((u64)raw_words);
   if (lane == 0) {
-    atomicAdd(&st->probes, s_probes); atomicAdd(&st->bucket_reads, s_reads); atomicAdd(&st->raw_words, s_raw);
-    if (s_text) atomicAdd(&st->text_hits, s_text);
+    atomicAdd(&st->probes, (u64)probes); atomicAdd(&st->bucket_reads, (u64)breads); atomicAdd(&st->raw_words, s_raw);
+    if (text_hits) atomicAdd(&st->text_hits, (u64)text_hits);
     atomicAdd(&st->wave_iters, (u64)wave_iters); atomicAdd(&st->lane_iters, (u64)lane_iters);
   }
 }
@@ -873,17 +910,44 @@ __global__ void k_mark_overflow(u32* raw, int raw_stride, u64 n_items) {
   const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_items) raw[i * (u64)raw_stride] = RAW_OVERFLOW;
 }
-// Kernel A of items [first, first + n) of the batch, on stream s: raw records into the items' slots
+// Every launch of kernel A that is queued before an earlier one has finished takes its positions from a cursor of its own: the chunks of a batch
+// (align_chunks, at most 64) are queued one behind the other on the caller's stream -- they run in order, but the host zeroes all their cursors once,
+// in front of the first -- and the second pass runs on its side stream, which does overlap the caller's.  The chunks' cursors are zeroed on the
+// caller's stream in front of the batch's first launch, the second pass's on its own stream in front of its launch.
+constexpr int MATCH_CURSORS = 65, MATCH_CURSOR_SECOND = 64;
+// The grid of a launch of kernel A over n positions.  Continuous feed: as many blocks as are resident at once (the kernel with this much dynamic
+// LDS), no more than there are grants; fixed chunks: a wavefront per chunk.
+template <class K>
+int match_grid(kamd_ctx* c, K kernel, size_t lds_bytes, u64 n, int items_per_wave, u32 grant, unsigned* grid) {
+  constexpr int WAVES = BLOCK / 64;
+  if (c->tune.match_continuous != 1) { *grid = grid_for((n + (u64)items_per_wave - 1) / (u64)items_per_wave, WAVES); return 0; }
+  // (blocks per CU depend on the instantiation and its dynamic LDS only: asked once per pair and context, a handful of entries)
+  int per_cu = 0;
+  for (const auto& e : c->match_occ) if (e.kernel == (const void*)kernel && e.lds_bytes == lds_bytes) per_cu = e.per_cu;
+  if (per_cu == 0) {
+    HIPC(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, BLOCK, lds_bytes));
+    per_cu = std::max(1, per_cu);
+    c->match_occ.push_back({(const void*)kernel, lds_bytes, per_cu});
+  }
+  u64 g = std::min<u64>((u64)std::max(1, c->n_cus) * (u64)std::max(1, per_cu), grid_for((n + (u64)grant - 1) / (u64)grant, WAVES));
+  if (c->tune.match_max_blocks > 0) g = std::min<u64>(g, (u64)c->tune.match_max_blocks);   // (test hook: a few wavefronts take every grant of a small batch)
+  *grid = (unsigned)std::max<u64>(g, 1);
+  return 0;
+}
+// Kernel A of items [first, first + n) of the batch, on stream s: raw records into the items' slots (launch k of the batch: its cursor)
 template <bool PAIRED, bool FILTER>
 int launch_match_chunk(kamd_ctx* c, hipStream_t s, const u32* d_words, const uint16_t* d_len, u64 first, u64 n, int seq_words, int rec_words, u32* slots,
-                       int stride) {
+                       int stride, int k) {
   constexpr int WAVES = BLOCK / 64;
   constexpr int NM = PAIRED ? 2 : 1;
   const int lane_words = seq_words * NM;
   size_t lds_bytes = ((size_t)WAVES * 64 * lane_words + (size_t)BLOCK * V3_LIST_CAP) * sizeof(u32);
   // diagnostic: unused LDS per block lowers the number of resident wavefronts (occupancy sensitivity; room for another stream's kernels)
   if (c->tune.lds_pad > 0 && lds_bytes <= 64 * 1024) lds_bytes = std::min<size_t>(64 * 1024, lds_bytes + (size_t)c->tune.lds_pad);
-  const u64 n_waves = (n + c->items_per_wave - 1) / c->items_per_wave;
+  const bool cont = c->tune.match_continuous == 1;
+  u32* const cursor = cont ? c->match_cursor.as<u32>() + k : nullptr;
+  const u32 grant = (u32)c->tune.match_grant;
+  unsigned grid = 0;
   const u32* w = d_words + first * (u64)(rec_words * NM);
   const uint16_t* l = d_len + first * NM;
   u32* raw = slots + first * (u64)stride;
@@ -895,8 +959,9 @@ int launch_match_chunk(kamd_ctx* c, hipStream_t s, const u32* d_words, const uin
 #define KAMD_LAUNCH_V3L(DLV, TXT, LAY)                                                                                                   \
   do {                                                                                                                                  \
     HIPC(hipFuncSetAttribute((const void*)k_match_v3<PAIRED, FILTER, DLV, TXT, LAY>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-    hipLaunchKernelGGL((k_match_v3<PAIRED, FILTER, DLV, TXT, LAY>), dim3(grid_for(n_waves, WAVES)), dim3(BLOCK), lds_bytes, s, c->ix, w, l, n, seq_words, \
-                       rec_words, c->items_per_wave, c->refill_min, raw, stride, c->stats_a.as<DevStatsA>());                           \
+    if (int rc = match_grid(c, k_match_v3<PAIRED, FILTER, DLV, TXT, LAY>, lds_bytes, n, c->items_per_wave, grant, &grid)) return rc;   \
+    hipLaunchKernelGGL((k_match_v3<PAIRED, FILTER, DLV, TXT, LAY>), dim3(grid), dim3(BLOCK), lds_bytes, s, c->ix, w, l, n, seq_words,  \
+                       rec_words, c->items_per_wave, c->refill_min, raw, stride, c->stats_a.as<DevStatsA>(), cursor, grant);           \
   } while (0)
 #define KAMD_LAUNCH_V3(DLV, TXT)                                                                                                         \
   do { if (c->ix.table_layout == kamd::LAYOUT_COMPACT) KAMD_LAUNCH_V3L(DLV, TXT, kamd::LAYOUT_COMPACT); else KAMD_LAUNCH_V3L(DLV, TXT, kamd::LAYOUT_WIDE); } while (0)
@@ -943,6 +1008,9 @@ template <bool PAIRED, bool FILTER>
 int align_batch(kamd_ctx* c, WorkStream& ws, const u32* d_words, const uint16_t* d_len, u64 n_items, int seq_words, int rec_words, const FilterDev& fd,
                 AlignOut& out, u64 key_base) {
   const int stride = 2 + V3_LIST_CAP + (FILTER ? 4 : 0);
+  // (kernel A keeps an item's position in 32 bits, in both of its launch forms: refused before anything is allocated or forked)
+  if (n_items >= kamd::FEED_MAX_ITEMS) return kamd::fail(-1, "kamd_pseudoalign: a batch must stay below 3 x 2^30 items (use smaller batches)");
+  if (int rc = c->match_cursor.ensure(MATCH_CURSORS * sizeof(u32), 0, c->stream)) return rc;
   // every item owns a fixed slot of the batch's record stream: raw record from k_match_v3, rewritten in place by k_classify.  The
   // stream belongs to this batch only (absorb_tuples moves what is new into the tuple store)
   if (int rc = c->stream_buf.ensure(n_items * (u64)stride * sizeof(u32), 0, c->stream)) return rc;
@@ -962,9 +1030,10 @@ int align_batch(kamd_ctx* c, WorkStream& ws, const u32* d_words, const uint16_t*
     if (int rc = ws.fork()) return rc;   // (behind push_state and whatever produced the reads on the caller's stream)
   }
   HIPC(hipEventRecord(c->ev0, ws.user));
+  if (c->tune.match_continuous == 1) HIPC(hipMemsetAsync(c->match_cursor.p, 0, (size_t)chunks * sizeof(u32), ws.user));
   for (int k = 0; k < chunks; k++) {
     const u64 first = (u64)k * per, n = std::min(per, n_items - first);
-    if (int rc = launch_match_chunk<PAIRED, FILTER>(c, ws.user, d_words, d_len, first, n, seq_words, rec_words, slots, stride)) return rc;
+    if (int rc = launch_match_chunk<PAIRED, FILTER>(c, ws.user, d_words, d_len, first, n, seq_words, rec_words, slots, stride, k)) return rc;
     if (chunks > 1) HIPC(hipEventRecord(c->al_ev_chunk[k], ws.user));
   }
   HIPC(hipEventRecord(c->ev1, ws.user));
@@ -1068,14 +1137,22 @@ int overflow_second_pass(kamd_ctx* c, hipStream_t s, bool side, const u32* d_wor
   HIPC(hipMemsetAsync(c->stats_b.p, 0, sizeof(DevStatsA), s));
   // items per wavefront: enough wavefronts for every CU, at least a wavefront's worth of items each
   // (8 / 16 / 32 wavefronts per CU measured alike on config #3 -- 0.15 M items -- and on 1.65 M stress items, 32 ahead by 1 %)
-  const int ipw = (int)std::min<u64>(1024, std::max<u64>(64, nov / ((u64)std::max(1, c->n_cus) * 32)));
-  const u64 n_waves = (nov + (u64)ipw - 1) / (u64)ipw;
+  // (continuous feed: the same figure bounds the grant, so that a few thousand long items still spread over the chip)
+  const bool cont = c->tune.match_continuous == 1;
+  const u64 spread = std::max<u64>(64, nov / ((u64)std::max(1, c->n_cus) * 32));
+  const int ipw = (int)std::min<u64>(1024, spread);
+  const u32 grant = (u32)std::min<u64>((u64)c->tune.match_grant, spread);
+  if (int rc = c->match_cursor.ensure(MATCH_CURSORS * sizeof(u32), 0, c->stream)) return rc;
+  u32* const cursor = cont ? c->match_cursor.as<u32>() + MATCH_CURSOR_SECOND : nullptr;
+  if (cont) HIPC(hipMemsetAsync(cursor, 0, sizeof(u32), s));
+  unsigned grid = 0;
   u32* raw2 = c->raw2.as<u32>();
 #define KAMD_LAUNCH_V3L2(DLV, TXT, LAY)                                                                                                  \
   do {                                                                                                                                  \
     HIPC(hipFuncSetAttribute((const void*)k_match_v3<PAIRED, FILTER, DLV, TXT, LAY, LC, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes)); \
-    hipLaunchKernelGGL((k_match_v3<PAIRED, FILTER, DLV, TXT, LAY, LC, true>), dim3(grid_for(n_waves, WAVES)), dim3(BLOCK), lds_bytes, s, c->ix, d_words, d_len, nov, \
-                       seq_words, rec_words, ipw, std::min(c->refill_min, 8), raw2, stride2, c->stats_b.as<DevStatsA>(), (const u64*)c->overflow_items.as<u64>()); \
+    if (int rc = match_grid(c, k_match_v3<PAIRED, FILTER, DLV, TXT, LAY, LC, true>, lds_bytes, nov, ipw, grant, &grid)) return rc;       \
+    hipLaunchKernelGGL((k_match_v3<PAIRED, FILTER, DLV, TXT, LAY, LC, true>), dim3(grid), dim3(BLOCK), lds_bytes, s, c->ix, d_words, d_len, nov, \
+                       seq_words, rec_words, ipw, std::min(c->refill_min, 8), raw2, stride2, c->stats_b.as<DevStatsA>(), cursor, grant, (const u64*)c->overflow_items.as<u64>()); \
   } while (0)
 #define KAMD_LAUNCH_V32(DLV, TXT)                                                                                                        \
   do { if (c->ix.table_layout == kamd::LAYOUT_COMPACT) KAMD_LAUNCH_V3L2(DLV, TXT, kamd::LAYOUT_COMPACT); else KAMD_LAUNCH_V3L2(DLV, TXT, kamd::LAYOUT_WIDE); } while (0)

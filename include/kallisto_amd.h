@@ -125,7 +125,7 @@ const char* kamd_last_error(void);
 /* The structures of this header are passed by pointer and have grown from round to round (kamd_tuning, kamd_profile): a binding compiled against
  * another version of the header must refuse to run rather than read or write beyond what it allocated.  kamd_abi_version() returns the
  * KAMD_ABI_VERSION the library was built with; callers compare it with the one they were compiled against (kallisto_amd/api.py does at load). */
-#define KAMD_ABI_VERSION 15
+#define KAMD_ABI_VERSION 16
 uint32_t kamd_abi_version(void);
 
 /* ---- S1: index ---- */
@@ -760,6 +760,12 @@ typedef struct {
   uint64_t n_frame_clashes;      /* MinCollector::cardinality_clashes: later frames as good as the winner at the moment they are visited */
   uint64_t n_winner[6];          /* pseudoaligned reads by winning frame */
   float last_translate_ms, last_match_ms;   /* the two kernels of the last batch */
+  /* which path the last call of kamd_pseudoalign_aa took (read-only; for tests that must know they reached a path): */
+  uint32_t last_chunks;          /* launches of the matching kernel: a call is cut into chunks of 262 144 reads */
+  uint32_t last_match_blocks;    /* blocks of four wavefronts in each of them: bounded by the chunk's groups of eight reads, by 4 x CUs and by the
+                                    class-list scratch */
+  uint32_t last_list_cap;        /* classes a frame's list may hold: min(1024, max_len - k + 2) */
+  uint32_t reserved;
 } kamd_aa_stats;
 int kamd_aa_stats_get(kamd_ctx*, kamd_aa_stats* out);
 

@@ -64,7 +64,7 @@ class Tuning(C.Structure):
 
 
 EM_FORMS = {"streamed": 1, "csr": 2, "local": 3}
-ABI_VERSION = 15   # KAMD_ABI_VERSION of include/kallisto_amd.h
+ABI_VERSION = 16  # KAMD_ABI_VERSION of include/kallisto_amd.h
 
 
 class _Profile(C.Structure):
@@ -85,7 +85,8 @@ class _Profile(C.Structure):
 class _AaStats(C.Structure):
     """kamd_aa_stats: what the translated search did with the reads since the last reset."""
     _fields_ = [("n_processed", C.c_uint64), ("n_rejected_offlist", C.c_uint64), ("n_all_empty", C.c_uint64), ("n_frame_clashes", C.c_uint64),
-                ("n_winner", C.c_uint64 * 6), ("last_translate_ms", C.c_float), ("last_match_ms", C.c_float)]
+                ("n_winner", C.c_uint64 * 6), ("last_translate_ms", C.c_float), ("last_match_ms", C.c_float),
+                ("last_chunks", C.c_uint32), ("last_match_blocks", C.c_uint32), ("last_list_cap", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class _ReadEcsStats(C.Structure):
@@ -932,7 +933,8 @@ class Context:
         _check(load_library().kamd_aa_stats_get(self._h, C.byref(s)), "kamd_aa_stats_get")
         return {"n_processed": int(s.n_processed), "n_rejected_offlist": int(s.n_rejected_offlist), "n_all_empty": int(s.n_all_empty),
                 "n_frame_clashes": int(s.n_frame_clashes), "n_winner": [int(x) for x in s.n_winner],
-                "translate_ms": float(s.last_translate_ms), "match_ms": float(s.last_match_ms)}
+                "translate_ms": float(s.last_translate_ms), "match_ms": float(s.last_match_ms),
+                "last_chunks": int(s.last_chunks), "last_match_blocks": int(s.last_match_blocks), "last_list_cap": int(s.last_list_cap)}
 
     # ---- BGZF input inflated on the device ----
     def bgzf_inflate(self, comp, members, text, comp_bytes=None, text_cap=None, debug_check_crc=None) -> dict:

@@ -186,6 +186,7 @@ extern "C" int kamd_pseudoalign_aa(kamd_ctx* c, const uint32_t* d_words, const u
   if (int rc = c->aa_scratch.ensure(blocks * BLOCK * (u64)cap * sizeof(u64), 0, c->stream)) return rc;
   HIPC(hipMemsetAsync(c->aa_ctr.p, 0, sizeof(AaCounters), c->stream));
   float tr_ms = 0.f, ma_ms = 0.f;
+  uint32_t launches = 0;
   for (u64 first = 0; first < n_reads; first += AA_CHUNK) {
     const u64 n = std::min(AA_CHUNK, n_reads - first);
     const u32* w = d_words + first * (u64)rec_words;
@@ -200,6 +201,7 @@ extern "C" int kamd_pseudoalign_aa(kamd_ctx* c, const uint32_t* d_words, const u
     hipLaunchKernelGGL(k_aa_match, dim3((unsigned)blocks), dim3(BLOCK), 0, c->stream, ix, (const u32*)c->aa_frames.as<u32>(), (const uint16_t*)c->aa_flen.as<uint16_t>(), l, n,
                        seq_words, rec_words, c->aa_scratch.as<u64>(), cap, (const uint8_t*)c->aa_offlist.as<uint8_t>(), out);
     HIPC(hipGetLastError());
+    ++launches;
     HIPC(hipEventRecord(c->aa_ev[2], c->stream));
     if (int rc = sync_state(c)) return rc;
     { float a = 0.f, b = 0.f; HIPC(hipEventElapsedTime(&a, c->aa_ev[0], c->aa_ev[1])); HIPC(hipEventElapsedTime(&b, c->aa_ev[1], c->aa_ev[2])); tr_ms += a; ma_ms += b; }
@@ -218,6 +220,7 @@ extern "C" int kamd_pseudoalign_aa(kamd_ctx* c, const uint32_t* d_words, const u
   s.n_processed += n_reads; s.n_rejected_offlist += ctr.rejected_offlist; s.n_all_empty += ctr.all_empty; s.n_frame_clashes += ctr.clashes;
   for (int j = 0; j < kamd::AA_FRAMES; j++) s.n_winner[j] += ctr.winner[j];
   s.last_translate_ms = tr_ms; s.last_match_ms = ma_ms;
+  s.last_chunks = launches; s.last_match_blocks = (uint32_t)blocks; s.last_list_cap = (uint32_t)cap;
   return 0;
 }
 
